@@ -8,6 +8,8 @@ pyramid for zooms 0..18 (heatmap.py:107-111 semantics), every non-empty cell
 written to HBM as (key, count).
 
     python bench.py                                   # 1 GPU, 1e9 points (config 2)
+    python bench.py --full                            # + count-sum check, measured HBM peak, CPU baseline
+    python bench.py --dump-outputs DIR                # + the last step's cells as DIR/*.npy
     python bench.py --gpus N                          # spawns N ranks itself
     python -m torch.distributed.run --nproc-per-node N bench.py --gpus N
         # N GPUs, 1.25e9 points per GPU (config 3 at N=8: 1e10), weak scaling:
@@ -33,8 +35,18 @@ steps, against the 8 TB/s HBM3E peak; `traffic` is the HBM bytes of one step
 from the committed rocprofv3 PMC summary (profiles/pmc_summary.json, FETCH_SIZE
 doubled per the gfx950 correction + WRITE_SIZE), or null.  `kernels` breaks the
 step down by stage from the library's own HIP events (hm_last_stats).
-`cpu_baseline` times the C oracle (oracle/hm_oracle.c, OpenMP) on a bounded
-sample of the same generator on this host's cores.
+
+A plain run sets up, warms up, times the steps and prints the line.  What takes
+work of its own runs only with `--full` and is null in the line otherwise:
+`pipeline.check` (every zoom's counts sum to the number of points),
+`roofline.measured_peak` (hm_bench_read and a 4 GiB torch copy) and
+`cpu_baseline`, which times the C oracle (oracle/hm_oracle.c, OpenMP) on a
+bounded sample of the same generator on this host's cores.
+
+`--dump-outputs DIR` writes the cells the last timed step returned, sorted by
+key, as float64 .npy files (dump_outputs below).  The cloud depends only on
+--kind, --points and --seed, so two builds run with the same arguments can be
+compared file for file.
 """
 from __future__ import annotations
 
@@ -64,9 +76,14 @@ def parse():
     ap.add_argument("--zmin", type=int, default=0)
     ap.add_argument("--zmax", type=int, default=18)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline figure does not need: the count-sum "
+                         "check, the measured HBM read peak and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's cells to DIR/<name>.npy (see dump_outputs)")
     ap.add_argument("--cpu-sample", type=float, default=2e8,
-                    help="points timed on the CPU oracle, ~10-30 s of host work (0 = skip)")
-    ap.add_argument("--no-check", action="store_true")
+                    help="with --full: points timed on the CPU oracle, ~10-30 s of host work (0 = skip)")
+    ap.add_argument("--no-check", action="store_true", help="with --full: skip the count-sum check")
     ap.add_argument("--force-dist", action="store_true",
                     help="run the RCCL merge path even with one rank (rehearsal of the N>1 code)")
     return ap.parse_args()
@@ -257,10 +274,62 @@ def measured_peak(torch, lat, lon, ctx, reps=5):
     return best, copy
 
 
+DUMP_CELLS = 1 << 20       # cells sampled by --dump-outputs: 5 float64 arrays of this length, 40 MiB
+DUMP_SEED = 0x5EED         # the sample's seed: the same positions for every run with the same cell count
+
+
+def dump_outputs(torch, path, bufs, m, zmin, zmax, suffix=""):
+    """Write what the last timed step returned (the first `m` entries of
+    bufs.keys / bufs.counts, bufs.nx records of bufs.xcells) as float64 .npy
+    files.  hm_count emits its cells in no fixed order, so they are sorted by
+    key (zoom, row, col) first; all values are integers below 2^53, exact in
+    float64.
+
+      zoom_totals.npy   (zooms, 5): zoom, cells inside the square, sum of their counts, cells outside
+                        it, sum of their counts -- over ALL cells; the two sums add up to the points
+      cells_index.npy   positions (in key order) of the cells below: all of them when m <= DUMP_CELLS,
+                        else DUMP_CELLS positions drawn once with DUMP_SEED, ascending
+      cells_zoom.npy, cells_row.npy, cells_col.npy, cells_count.npy   those cells
+      outside_cells.npy (k, 4): zoom, row, col, count of the cells outside [0, 2^z)^2, sorted (first
+                        DUMP_CELLS of them); written only when there are any
+    """
+    from heatmap_amd import device
+
+    os.makedirs(path, exist_ok=True)
+    keys, order = torch.sort(bufs.keys[:m])
+    counts = bufs.counts[:m][order]
+    zoom = keys >> 58
+    ncell = torch.bincount(zoom, minlength=64)
+    nsum = torch.zeros(64, dtype=torch.int64, device=keys.device).index_add_(0, zoom, counts)
+    zs = np.arange(zmin, zmax + 1)
+    x = bufs.xcells[:4 * bufs.nx].cpu().numpy().reshape(-1, 4)
+    x = x[np.lexsort((x[:, 2], x[:, 1], x[:, 0]))]
+    xz = x[:, 0].astype(np.int64)
+    totals = np.stack([zs, ncell.cpu().numpy()[zs], nsum.cpu().numpy()[zs], np.bincount(xz, minlength=64)[zs],
+                       np.bincount(xz, weights=x[:, 3], minlength=64)[zs]], axis=1).astype(np.float64)
+    if m > DUMP_CELLS:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(m, DUMP_CELLS, replace=False))
+    else:
+        idx = np.arange(m)
+    sel = torch.from_numpy(idx).to(keys.device)
+    z, r, c = device.decode_keys(keys[sel].cpu().numpy().view(np.uint64))
+    arrays = {"zoom_totals": totals, "cells_index": idx, "cells_zoom": z, "cells_row": r, "cells_col": c,
+              "cells_count": counts[sel].cpu().numpy()}
+    if len(x):
+        arrays["outside_cells"] = x[:DUMP_CELLS]
+    elif os.path.exists(os.path.join(path, "outside_cells" + suffix + ".npy")):
+        os.remove(os.path.join(path, "outside_cells" + suffix + ".npy"))   # an earlier dump's, into the same DIR
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + suffix + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def main():
     args = parse()
     if args.gpus < 1:
         print("bench.py: --gpus must be >= 1", file=sys.stderr)
+        sys.exit(2)
+    if args.steps < 1 or args.warmup < 0:
+        print("bench.py: --steps must be >= 1 and --warmup >= 0", file=sys.stderr)
         sys.exit(2)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn(args))
@@ -351,8 +420,10 @@ def main():
         dt = time.perf_counter() - t0
         step_ms_ev = ev0.elapsed_time(ev1) / args.steps
         cells = cells_rank = int(m)
+    if args.dump_outputs:
+        dump_outputs(torch, args.dump_outputs, bufs, m, args.zmin, args.zmax, "" if ws == 1 else "_rank%d" % rank)
     check = None
-    if not args.no_check:
+    if args.full and not args.no_check:
         # every zoom's counts sum to the number of points (over all ranks' owned cells)
         tot_t = bufs.counts[:m].sum().reshape(1)
         if args.dist:
@@ -366,9 +437,15 @@ def main():
     st = np.mean(np.array(stages), axis=0)
     tag = "%s_%d_z%d-%d" % (args.kind, per, args.zmin, args.zmax)
     traffic, traffic_src, fp64 = profile_traffic(tag)
-    peak_meas, copy_meas = measured_peak(torch, lat, lon, ctx)
     alg_step = ALG_BYTES_PER_POINT * per + ALG_BYTES_PER_CELL * cells_rank      # one rank's step
     achieved = alg_step / (step_ms_ev * 1e-3) / 1e9
+    peak = None                # a measurement of its own (hm_bench_read + a 4 GiB torch copy): --full only
+    if args.full:
+        peak_meas, copy_meas = measured_peak(torch, lat, lon, ctx)
+        peak = {"GBps": peak_meas, "frac": achieved / peak_meas,
+                "how": "hm_bench_read: HIP read-stream kernel over the resident lat/lon "
+                       "(16-B loads, K1's access shape), best of 5",
+                "torch_copy_GBps": copy_meas}
     kernels = {
         "k_project_partition": {"us": float(st[0]), "alg_bytes": ALG_BYTES_PER_POINT * per,
                                 "GBps": ALG_BYTES_PER_POINT * per / (st[0] * 1e-6) / 1e9 if st[0] else None},
@@ -384,6 +461,7 @@ def main():
         "n_gpus": ws,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": args.full,
         "ms_per_step": ms,
         "higher_is_better": True,
         "scaling": "weak",
@@ -399,18 +477,14 @@ def main():
                      "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
                      "traffic": traffic, "traffic_source": traffic_src, "avg_launch_us": step_ms_ev * 1e3,
                      "alg_bytes_per_launch": alg_step, "cells_per_step": cells_rank,
-                     "measured_peak": {"GBps": peak_meas, "frac": achieved / peak_meas,
-                                       "how": "hm_bench_read: HIP read-stream kernel over the resident lat/lon "
-                                              "(16-B loads, K1's access shape), best of 5",
-                                       "torch_copy_GBps": copy_meas},
-                     "fp64": fp64},
+                     "measured_peak": peak, "fp64": fp64},
         "kernels": kernels,
         "pipeline": {"slow_path_points": ctx.last_stats()[0], "level1_reruns": reruns, "check": check},
     }
     if dist_info is not None:
         out["distributed"] = dist_info
     if rank == 0:
-        out["cpu_baseline"] = cpu_baseline(args, lat, lon)
+        out["cpu_baseline"] = cpu_baseline(args, lat, lon) if args.full else None
         print(json.dumps(out), flush=True)
     barrier(ws)
 

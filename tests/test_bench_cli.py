@@ -31,6 +31,18 @@ def test_world_size_mismatch_is_an_error():
     assert "WORLD_SIZE=4 but --gpus 2" in r.stderr
 
 
+def test_zero_steps_is_an_error():
+    r = _run(["--gpus", "1", "--steps", "0"])
+    assert r.returncode == 2
+    assert "--steps must be >= 1" in r.stderr
+
+
+def test_full_and_dump_outputs_are_options():
+    r = _run(["--help"])
+    assert r.returncode == 0
+    assert "--full" in r.stdout and "--dump-outputs DIR" in r.stdout
+
+
 def test_too_few_gpus_is_an_error():
     import torch
 

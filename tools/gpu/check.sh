@@ -13,7 +13,7 @@ timeout -k 10 600 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout
 rc=$?
 tail -5 "$O/pytest.log"
 [ $rc -ne 0 ] && exit $rc
-timeout -k 10 300 python -u bench.py --cpu-sample 0 > "$O/bench.log" 2>&1 || { tail -20 "$O/bench.log"; exit 1; }
+timeout -k 10 300 python -u bench.py --full --cpu-sample 0 > "$O/bench.log" 2>&1 || { tail -20 "$O/bench.log"; exit 1; }
 tail -1 "$O/bench.log" | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read())

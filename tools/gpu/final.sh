@@ -12,7 +12,7 @@ mkdir -p "$O"
 echo "== smoke"
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" 2>&1 | grep -v amdgpu.ids | tail -3 || exit 1
 echo "== default bench"
-timeout -k 10 400 python -u bench.py > "$O/bench_default.log" 2>&1 || { tail -20 "$O/bench_default.log"; exit 1; }
+timeout -k 10 400 python -u bench.py --full > "$O/bench_default.log" 2>&1 || { tail -20 "$O/bench_default.log"; exit 1; }
 tail -1 "$O/bench_default.log" | cut -c1-400
 bash tools/gpu/profile_round.sh "$TAG" || exit 1
 bash tools/gpu/pmc.sh "${TAG}_pmc" > /dev/null || exit 1

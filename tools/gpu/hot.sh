@@ -12,11 +12,11 @@ timeout -k 10 600 python -u -m pytest -x -q --timeout 200 --timeout-method threa
 rc=$?; tail -5 "$O/pytest_hot.log"; [ $rc -eq 0 ] || exit $rc
 for h in 0 1; do
   echo "== bench hotspots HM_HOT=$h"
-  HM_HOT=$h timeout -k 10 300 python -u bench.py --steps 10 --warmup 3 --cpu-sample 0 > "$O/bench_hot$h.log" 2>&1 || { tail -20 "$O/bench_hot$h.log"; exit 1; }
+  HM_HOT=$h timeout -k 10 300 python -u bench.py --full --steps 10 --warmup 3 --cpu-sample 0 > "$O/bench_hot$h.log" 2>&1 || { tail -20 "$O/bench_hot$h.log"; exit 1; }
   tail -1 "$O/bench_hot$h.log" | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['ms_per_step'], d['roofline']['frac'], d['pipeline'], json.dumps(d['kernels']))"
 done
 echo "== bench skew"
-timeout -k 10 300 python -u bench.py --kind skew --steps 5 --warmup 2 --cpu-sample 0 > "$O/bench_skew.log" 2>&1 || { tail -20 "$O/bench_skew.log"; exit 1; }
+timeout -k 10 300 python -u bench.py --full --kind skew --steps 5 --warmup 2 --cpu-sample 0 > "$O/bench_skew.log" 2>&1 || { tail -20 "$O/bench_skew.log"; exit 1; }
 tail -1 "$O/bench_skew.log" | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['ms_per_step'], d['roofline']['frac'], d['pipeline'], json.dumps(d['kernels']))"
 echo "== rest of the gpu tests"
 timeout -k 10 900 python -u -m pytest -x -q --timeout 200 --timeout-method thread -m gpu tests > "$O/pytest_gpu.log" 2>&1

@@ -10,7 +10,7 @@ O="$R/gpurun_out/$TAG"
 mkdir -p "$O"
 cd "$R"
 echo "== bench"
-timeout -k 10 400 python -u bench.py "$@" > "$O/bench.log" 2>&1 || { tail -30 "$O/bench.log"; exit 1; }
+timeout -k 10 400 python -u bench.py --full "$@" > "$O/bench.log" 2>&1 || { tail -30 "$O/bench.log"; exit 1; }
 tail -1 "$O/bench.log"
 cd /tmp
 echo "== kernel trace"
