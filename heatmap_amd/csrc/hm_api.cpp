@@ -170,6 +170,7 @@ enum {
     B_RT_CNT, B_RT_OFF, B_MG_TABLE, B_MG_STATE, B_SEG, B_RS_BIG,
     B_HOT, B_HOT_COUNTS, B_HOT_PARENT, B_D2B, B_MB_CNT, B_MB_OFF, B_MB_KEYS, B_MB_COUNTS, B_MB_CNT2, B_MB_OFF2,
     B_MB_KEYS2, B_MB_COUNTS2, B_KEYS_C, B_HOT_FORCE, B_C2B, B_SEG2, B_CTOT, B_CBASE, B_CCUR, B_MG_PIECES,
+    B_L1_SLOT,
     B_COUNT
 };
 
@@ -825,6 +826,8 @@ static int count_impl(hm_ctx* ctx, const double* lat, const double* lon, const i
             ENSURE(B_L1_RCAP, FS * 4, rcap);
             ENSURE(B_L1_HIST, HM_D1 * 4, hist);
             ENSURE(B_L1_SMASK, HM_D1, smask);
+            uint4* l1slot = nullptr;   /* k_l1_fast's slot table (lat/lon input) */
+            if (HM_L1_SLOTTAB && !from_tiles) ENSURE(B_L1_SLOT, (size_t)FS * sizeof(uint4), l1slot);
             /* hot tiles are level-2 buckets: zoom zs[1], a dense sample
              * histogram of <= 4^11 tiles.  In the two-level plan (level 1 at
              * z1, the last at zb) they skip every partition after level 1; in
@@ -856,6 +859,7 @@ static int count_impl(hm_ctx* ctx, const double* lat, const double* lon, const i
             a.rbase = rbase;
             a.rcap = rcap;
             a.smask = smask;
+            a.l1slot = l1slot;
             a.overflow = ctx->state + ST_OVERFLOW;
             a.err_word = ctx->state + ST_ERR;
             a.x = xl;
@@ -934,6 +938,7 @@ static int count_impl(hm_ctx* ctx, const double* lat, const double* lon, const i
                            (double)(F + (hot_on ? HM_MAX_HOT : 0)) * HM_L1_ZERO_SAMPLES * (double)stride + 1024.0;
             hm_launch_l1_sizes(s, hist, F, hot_on ? hot_n : nullptr, stride, rcap, rbase, smask,
                                ctx->state + ST_L1TOTAL);
+            if (l1slot) hm_launch_l1_slots(s, a);
             HIPCHK(hipGetLastError());
             if (bound >= (double)0xFFF00000ull) {
                 /* the bound passes the u32 key positions (n above ~1.5e9):
@@ -995,6 +1000,7 @@ static int count_impl(hm_ctx* ctx, const double* lat, const double* lon, const i
                     if (total_cap >= 0xFFF00000ull) return HM_FALLBACK;
                     HIPCHK(hipMemcpyAsync(rcap, hc, FS * 4, hipMemcpyHostToDevice, s));
                     HIPCHK(hipMemcpyAsync(rbase, hb, FS * 4, hipMemcpyHostToDevice, s));
+                    if (l1slot) hm_launch_l1_slots(s, a);   /* the table holds the regions' bases and sizes */
                 }
                 ENSURE(slot_k ? B_KEYS_B : B_KEYS_A, (total_cap + 8) * (V.out16 ? 2 : 4), kout);
                 a.keys_out = kout;

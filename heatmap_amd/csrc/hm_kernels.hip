@@ -56,6 +56,14 @@ extern "C" int hm_debug_stamps(void* host, size_t bytes)
 {
     return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_stamps), bytes, 0, hipMemcpyDeviceToHost);
 }
+#elif defined(HM_ISA_MARKS)
+/* tools/isa_phases.py: the stamp sites of kernel HM_ISA_MARKS (numbered as
+ * HM_STAMPS) as assembly comments; the build is only ever read, not run */
+#define HM_STAMP_M(m, k)                                                                       \
+    do {                                                                                       \
+        if (HM_ISA_MARKS == (m)) asm volatile("; hm_phase_mark " #k);                          \
+    } while (0)
+#define HM_STAMP_V(m, k, v) do { } while (0)
 #else
 #define HM_STAMP_M(m, k) do { } while (0)
 #define HM_STAMP_V(m, k, v) do { } while (0)
@@ -129,6 +137,35 @@ __device__ __forceinline__ uint32_t hm_opaque(uint32_t x)
 {
     asm volatile("" : "+v"(x));
     return x;
+}
+
+/* every x[k] materialised at this point, as ONE opaque statement: LDS reads
+ * issued before it are all waited for with a single s_waitcnt, and none can
+ * sink below it (k_l1_fast's copy-out) */
+#define HM_PIN16(x)                                                                                                   \
+    "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3]), "+v"(x[4]), "+v"(x[5]), "+v"(x[6]), "+v"(x[7]), "+v"(x[8]),       \
+        "+v"(x[9]), "+v"(x[10]), "+v"(x[11]), "+v"(x[12]), "+v"(x[13]), "+v"(x[14]), "+v"(x[15])
+template <int N>
+__device__ __forceinline__ void hm_pin_all(uint32_t (&x)[N])
+{
+    if constexpr (N == 16) {
+        asm volatile("" : HM_PIN16(x));
+    } else {
+#pragma unroll
+        for (int k = 0; k < N; k++) asm volatile("" : "+v"(x[k]));
+    }
+}
+/* ... and one more value with them */
+template <int N>
+__device__ __forceinline__ void hm_pin_all(uint32_t (&x)[N], uint32_t& y)
+{
+    if constexpr (N == 16) {
+        asm volatile("" : HM_PIN16(x), "+v"(y));
+    } else {
+#pragma unroll
+        for (int k = 0; k < N; k++) asm volatile("" : "+v"(x[k]));
+        asm volatile("" : "+v"(y));
+    }
 }
 
 /* the point stream: 16 GB per 1e9 points read once, with the non-temporal
@@ -601,6 +638,45 @@ static_assert(HM_L1_SLOTS % HM_P1_THREADS == 0, "slots per thread");
 #ifndef HM_L1_WAVES
 #define HM_L1_WAVES 4                       /* k_l1_fast: waves per SIMD its registers allow (4: 2 blocks of 8 waves per CU) */
 #endif
+#ifndef HM_L1_COPY_BATCH
+#define HM_L1_COPY_BATCH 1                  /* copy-out: 16 entry reads, 16 delta reads, then the stores */
+#endif
+
+/* k_l1_fast's slot -> level-1 digit (hot slot h: digit HM_MAX_F1 + h; cold
+ * slot: the bank skew undone), wd = dbits / 2 */
+__device__ __forceinline__ uint32_t hm_l1_slot_digit(uint32_t sl, int wd)
+{
+    if (sl < HM_MAX_HOT) return HM_MAX_F1 + sl;
+    const uint32_t u = sl - HM_MAX_HOT, m = (1u << wd) - 1u;
+    return HM_SKEW_CUR ? ((u & ~m) | ((u - ((u >> wd) << 3)) & m)) : u;
+}
+__device__ __forceinline__ bool hm_l1_slot_live(uint32_t sl, uint32_t H, uint32_t F)
+{
+    return sl < HM_MAX_HOT ? sl < H : (sl - HM_MAX_HOT) < F;
+}
+
+/* the slot table of one call (HM_L1_SLOTTAB, hm_pipeline.h): 8 x 1536 entries,
+ * what every one of k_l1_fast's blocks used to work out for itself from
+ * rbase, rcap and smask with five dependent scattered loads per slot */
+__global__ __launch_bounds__(256) void k_l1_slots(HmPart1Args a, uint4* __restrict__ tab)
+{
+    const uint32_t sl = blockIdx.x * 256u + threadIdx.x, b = blockIdx.y;
+    if (sl >= HM_D1) return;
+    const uint32_t H = a.hot_z >= 0 ? min(*a.hot_n, (uint32_t)HM_MAX_HOT) : 0u;
+    uint4 e = make_uint4(0u, 0u, 0u, 0u);
+    if (hm_l1_slot_live(sl, H, 1u << a.dbits)) {
+        const uint32_t d = hm_l1_slot_digit(sl, a.dbits >> 1);
+        const uint32_t i = hm_l1i(d, a.smask[d] != 0 ? b : 0u);
+        e = make_uint4(a.rbase[i], a.rcap[i], i, 0u);
+    }
+    tab[b * HM_D1 + sl] = e;
+}
+
+void hm_launch_l1_slots(hipStream_t s, const HmPart1Args& a)
+{
+    static_assert(HM_D1 == HM_MAX_HOT + HM_MAX_F1, "the table's rows are k_l1_fast's slots");
+    hipLaunchKernelGGL(k_l1_slots, dim3((HM_D1 + 255) / 256, HM_L1_SHARDS), dim3(256), 0, s, a, (uint4*)a.l1slot);
+}
 template <typename OutT, bool KEEP>
 __global__ __launch_bounds__(HM_P1_THREADS) __attribute__((amdgpu_waves_per_eu(HM_L1_WAVES, HM_L1_WAVES))) void
 k_l1_fast(HmPart1Args a)
@@ -639,14 +715,14 @@ k_l1_fast(HmPart1Args a)
     constexpr int PERD = HM_L1_SLOTS / HM_P1_THREADS;
     const int wd = a.dbits >> 1;
     /* slot -> digit (hot slot h: digit HM_MAX_F1 + h; cold slot: unskewed) */
-    auto digit_of = [&](uint32_t sl) -> uint32_t {
-        if (sl < HM_MAX_HOT) return HM_MAX_F1 + sl;
-        const uint32_t u = sl - HM_MAX_HOT, m = (1u << wd) - 1u;
-        return HM_SKEW_CUR ? ((u & ~m) | ((u - ((u >> wd) << 3)) & m)) : u;
-    };
-    auto live = [&](uint32_t sl) {
-        return sl < HM_MAX_HOT ? sl < H : (sl - HM_MAX_HOT) < (uint32_t)F;
-    };
+    auto digit_of = [&](uint32_t sl) -> uint32_t { return hm_l1_slot_digit(sl, wd); };
+    /* HM_L1_SLOTTAB: no liveness test anywhere.  A point's slot is a dummy, a
+     * hot tile the table holds (h < H) or the cold slot of its own digit
+     * (< F: an accepted point has r, c < 2^Z), so a dead slot's count word
+     * stays 0: it reserves nothing, its zero capacity fits its zero count,
+     * and the stage offset and delta it writes to its own words are never
+     * read */
+    auto live = [&](uint32_t sl) { return HM_L1_SLOTTAB ? true : hm_l1_slot_live(sl, H, (uint32_t)F); };
     /* keep bytes, then the tables, then the points (vmcnt retires in order) */
     uint32_t kp[HM_P1_PPT / 2];   /* KEEP: the keep bytes (a keep-less call compiles the test away) */
     if (KEEP) {
@@ -665,6 +741,17 @@ k_l1_fast(HmPart1Args a)
         const int i = q * HM_P1_THREADS + tid;
         tv[q] = i >= HM_YTAB_N ? __builtin_nan("") : c_ytab[i];
     }
+#if HM_L1_SLOTTAB
+    /* the owned slots' (base, capacity, fill index): one coalesced 16-B load
+     * each; no address depends on a load, so nothing waits before the point
+     * loads are out */
+    uint4 st[PERD];
+    {
+        const uint4* const row = a.l1slot + (blockIdx.x & (HM_L1_SHARDS - 1)) * HM_L1_SLOTS;
+#pragma unroll
+        for (int q = 0; q < PERD; q++) st[q] = row[q * HM_P1_THREADS + tid];
+    }
+#else
     uint32_t smk[PERD], rcap2[PERD][2], rbase2[PERD][2];
 #pragma unroll
     for (int q = 0; q < PERD; q++) {
@@ -678,10 +765,24 @@ k_l1_fast(HmPart1Args a)
         rbase2[q][0] = lv ? a.rbase[s0] : 0u;
         rbase2[q][1] = lv ? a.rbase[s1] : 0u;
     }
+#endif
     constexpr int HV = HM_HOT_SLOTS / 4 / HM_P1_THREADS;
     uint4 hv[HV];
+#if HM_L1_SLOTTAB
+    /* no branch around the loads (the join of "loaded" and "zero" cost an
+     * s_waitcnt vmcnt(0) ahead of the point loads): without hot tiles they
+     * read the first 16 KB of rbase, HM_D1 * HM_L1_SHARDS words, unused */
+    static_assert(HM_HOT_SLOTS <= HM_D1 * HM_L1_SHARDS, "the stand-in array holds a hot table's bytes");
+    const uint4* const hsrc = H ? (const uint4*)a.hot_hash : (const uint4*)a.rbase;
+#pragma unroll
+    for (int j = 0; j < HV; j++) {
+        const uint4 v = hsrc[j * HM_P1_THREADS + tid];
+        hv[j] = make_uint4(v.x, v.y, v.z, v.w);
+    }
+#else
 #pragma unroll
     for (int j = 0; j < HV; j++) hv[j] = H ? ((const uint4*)a.hot_hash)[j * HM_P1_THREADS + tid] : make_uint4(0u, 0u, 0u, 0u);
+#endif
     __builtin_amdgcn_sched_barrier(0);
     double2 la[HM_P1_PPT / 2], lo[HM_P1_PPT / 2];
     {
@@ -810,11 +911,15 @@ k_l1_fast(HmPart1Args a)
 #pragma unroll
     for (int q = 0; q < PERD; q++) {
         const uint32_t sl = q * HM_P1_THREADS + tid;
-        const uint32_t d = digit_of(sl);
-        const uint32_t sh = smk[q] != 0 ? (blockIdx.x & (HM_L1_SHARDS - 1)) : 0u;
         cnt[q] = live(sl) ? cw[sl] : 0u;
         gpos[q] = 0;
+#if HM_L1_SLOTTAB
+        if (cnt[q]) gpos[q] = atomicAdd(&a.fill[st[q].z], cnt[q]);
+#else
+        const uint32_t d = digit_of(sl);
+        const uint32_t sh = smk[q] != 0 ? (blockIdx.x & (HM_L1_SHARDS - 1)) : 0u;
         if (cnt[q]) gpos[q] = atomicAdd(&a.fill[hm_l1i(d, sh)], cnt[q]);
+#endif
     }
     /* stage offsets: cold slots (q >= QH) first, hot slots (q < QH) after
      * them, from one scan of (cold count | hot count << 16) */
@@ -844,8 +949,12 @@ k_l1_fast(HmPart1Args a)
         for (int q = 0; q < PERD; q++) {
             const uint32_t sl = q * HM_P1_THREADS + tid;
             if (live(sl)) {
+#if HM_L1_SLOTTAB
+                const uint32_t rc = st[q].y, rb = st[q].x;
+#else
                 const uint32_t rc = smk[q] != 0 ? rcap2[q][1] : rcap2[q][0];
                 const uint32_t rb = smk[q] != 0 ? rbase2[q][1] : rbase2[q][0];
+#endif
                 const bool fits = (uint64_t)gpos[q] + cnt[q] <= (uint64_t)rc;
                 over |= cnt[q] && !fits;
                 cw[HM_L1_CW + sl] = (fits ? rb + gpos[q] : 0xFFF00000u) - offq[q];
@@ -868,6 +977,9 @@ k_l1_fast(HmPart1Args a)
      * entry.  HM_L1_LATE_DEST: the entry holds its slot, and the destination
      * deltas are written after the staging, so the reservation atomics'
      * round trip overlaps it (the copy-out looks the delta up per key) */
+    /* (the compiler reads each offset under its point's select, one LDS
+     * round trip per point; all 16 reads ahead of one wait measured no
+     * faster: DESIGN.md 3.1, round 7) */
 #pragma unroll
     for (int k = 0; k < HM_P1_PPT; k++) {
         const uint32_t o = cw[slot[k]];   /* (dummies: in range, unused) */
@@ -898,14 +1010,37 @@ k_l1_fast(HmPart1Args a)
         else *(uint16_t*)(houtb + (uint64_t)e.y * 2u) = (uint16_t)hk;
     };
     uint2 e[HM_P1_PPT];
+    uint32_t sov;   /* s_over (the overflow flag rides in the delta batch) */
+    if (HM_L1_COPY_BATCH && HM_L1_LATE_DEST) {
+        /* three batches: the 16 entries, their 16 deltas, then the stores,
+         * with one wait between them.  An entry past total is stale stage
+         * (table words): its delta index is clamped into cw, not branched
+         * around, and what it reads is never stored */
+        uint32_t dl[HM_P1_PPT];
 #pragma unroll
-    for (int j = 0; j < HM_P1_PPT; j++) {
-        const uint32_t i = j * HM_P1_THREADS + tid;
-        e[j] = ent[i];   /* past total: unused */
-        if (HM_L1_LATE_DEST) e[j].y = i < total ? cw[HM_L1_CW + e[j].y] + i : 0u;
+        for (int j = 0; j < HM_P1_PPT; j++) {
+            e[j] = ent[j * HM_P1_THREADS + tid];
+            dl[j] = e[j].y;
+        }
+        hm_pin_all(dl);   /* (the key comes with the slot: one 8-B read) */
+#pragma unroll
+        for (int j = 0; j < HM_P1_PPT; j++) dl[j] = cw[HM_L1_CW + min(dl[j], (uint32_t)(HM_L1_CW - 1))];
+        sov = s_over;
+        hm_pin_all(dl, sov);
+        sov = __builtin_amdgcn_readfirstlane(sov);   /* block-uniform: a scalar branch, as before */
+#pragma unroll
+        for (int j = 0; j < HM_P1_PPT; j++) e[j].y = dl[j] + (uint32_t)(j * HM_P1_THREADS + tid);
+    } else {
+#pragma unroll
+        for (int j = 0; j < HM_P1_PPT; j++) {
+            const uint32_t i = j * HM_P1_THREADS + tid;
+            e[j] = ent[i];   /* past total: unused */
+            if (HM_L1_LATE_DEST) e[j].y = i < total ? cw[HM_L1_CW + e[j].y] + i : 0u;
+        }
+        sov = s_over;
     }
     const uint32_t wofs = (uint32_t)tid & ~63u;
-    if (!s_over) {
+    if (!sov) {
 #pragma unroll
         for (int j = 0; j < HM_P1_PPT; j++) {
             const uint32_t wb = __builtin_amdgcn_readfirstlane(j * HM_P1_THREADS + wofs);

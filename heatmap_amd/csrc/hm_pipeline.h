@@ -69,6 +69,15 @@ static_assert(HM_HOT_BUCKETS == 1 << HM_HOT_BBITS, "hot-tile table");
  * digits one wave reserves for sit in consecutive words, so its returning
  * atomics coalesce into a few 64-B requests instead of one per digit */
 __host__ __device__ inline uint32_t hm_l1i(uint32_t d, uint32_t sh) { return sh * HM_D1 + d; }
+/* k_l1_fast's per-call slot table (k_l1_slots): for block shard b = block & 7
+ * and the kernel's own slot s (hot tiles first, then the bank-skewed cold
+ * digits), entry [b * HM_D1 + s] = (region base, region capacity, index of
+ * the fill word with the shard already chosen, 0); a dead slot is all zero.
+ * 196 KB: it stays in L2.  0: every block derives the same from rbase, rcap
+ * and smask (rounds 4-6) */
+#ifndef HM_L1_SLOTTAB
+#define HM_L1_SLOTTAB 1
+#endif
 /* levels >= 2 */
 #ifndef HM_PN_THREADS
 #define HM_PN_THREADS 1024
@@ -257,6 +266,7 @@ struct HmPart1Args {
     const uint32_t* rbase;    /* [HM_D1 * HM_L1_SHARDS] */
     const uint32_t* rcap;     /* [HM_D1 * HM_L1_SHARDS] */
     const uint8_t* smask;     /* [F]: shards of digit d - 1 (0 or HM_L1_SHARDS - 1) */
+    const uint4* l1slot;      /* [HM_L1_SHARDS * HM_D1] k_l1_fast's slot table (HM_L1_SLOTTAB), lat/lon input */
     unsigned long long* overflow;
     unsigned long long* err_word;
     HmExotic x;
@@ -471,6 +481,9 @@ void hm_launch_sample_digits(hipStream_t s, const HmPart1Args& a, uint64_t strid
 void hm_launch_hot_select(hipStream_t s, const HmHotArgs& a);
 /* region sizes of the F cold digits and (hot_n) the hot tiles' digits; their
  * total -> *total */
+/* the slot table from the sized regions (after hm_launch_l1_sizes, or after
+ * the host rewrote rcap / rbase for an overflow re-run) */
+void hm_launch_l1_slots(hipStream_t s, const HmPart1Args& a);
 void hm_launch_l1_sizes(hipStream_t s, const uint32_t* hist, int F, const uint32_t* hot_n, uint64_t stride,
                         uint32_t* rcap, uint32_t* rbase, uint8_t* smask, unsigned long long* total);
 void hm_launch_hot_nr(hipStream_t s, const HmHotRunArgs& a);

@@ -29,6 +29,7 @@ NAMES = {
     "stamps2": ["start", "item+loads_issue+init", "count_rank(loads)", "barrier", "scan+run_atomics", "scatter",
                 "copy+runs"],
     "stamps4": ["start", "issue+lds_setup", "project(loads)", "redo+count_rank", "reserve+scan", "stage", "copy"],
+    "stamps4r6": ["start", "issue+lds_setup", "project(loads)", "redo+count_rank", "reserve+scan", "stage", "copy"],
     "stamps5": ["start", "zero+item", "count(stream_runs)", "squeeze", "pyramid+emit"],
     "stamps6": [],
     "stamps6w8": [],

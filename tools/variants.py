@@ -92,6 +92,11 @@ VARIANTS = {
     "cs2it12": ["HM_CS2_IT=12"],
     "l1nt0": ["HM_L1_NT=0"],                        # K1's point loads without the non-temporal hint
     "l1early": ["HM_L1_LATE_DEST=0"],
+    # k_l1_fast's serial chains (round 7): each change off on its own, and both off (round 6's kernel)
+    "l1noslottab": ["HM_L1_SLOTTAB=0"],             # every block derives its slots' regions from rbase / rcap / smask
+    "l1nocopybatch": ["HM_L1_COPY_BATCH=0"],        # copy-out: entry and delta reads per key
+    "l1r6": ["HM_L1_SLOTTAB=0", "HM_L1_COPY_BATCH=0"],
+    "stamps4r6": ["HM_STAMPS=4", "HM_L1_SLOTTAB=0", "HM_L1_COPY_BATCH=0"],
     "sh8": ["HM_L1_SHARD_TILES=8"],                 # level-1 digits sharded above 8 tiles of points (default 64)
     "sh2": ["HM_L1_SHARD_TILES=2"],
     "lb1": ["HM_OS_LB=1"],                           # one-sweep look-back: one predecessor per round trip
@@ -134,7 +139,7 @@ PATCHES["l1nostore"] = [
      "auto put_cold = [&](uint2 e) { if (e.x == 0xFFFFFFFFu && e.y == 0x1234567u) *(OutT*)outb = (OutT)e.x; };"),
     ("hm_kernels.hip", "        *(uint16_t*)(houtb + (uint64_t)e.y * 2u) = (uint16_t)hk;",
      "        if (hk == 0xFFFFFFFFu && e.y == 0x1234567u) *(uint16_t*)houtb = (uint16_t)hk;")]
-PATCHES["l1noatom"] = [("hm_kernels.hip", "        if (cnt[q]) gpos[q] = atomicAdd(&a.fill[hm_l1i(d, sh)], cnt[q]);",
+PATCHES["l1noatom"] = [("hm_kernels.hip", "        if (cnt[q]) gpos[q] = atomicAdd(&a.fill[st[q].z], cnt[q]);",
                         "        if (cnt[q]) gpos[q] = 0;")]
 # k_small_pairs timing builds: no cursor atomic (a made-up base), no cell
 # stores, no emit pass at all (profiles/r6/small_pairs_atomics_ab.jsonl has
