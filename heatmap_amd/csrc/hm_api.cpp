@@ -2232,6 +2232,7 @@ struct hm_stream {
     uint32_t base = 0;
     unsigned long long* state = nullptr;  /* device HMS_ST_* words */
     HmsBuckets bk{};                      /* (group, period) buckets */
+    uint64_t* bk_alt = nullptr;           /* hm_stream_expire: the fresh table the survivors' buckets move to */
     uint32_t *bflag = nullptr, *blist = nullptr, *bloc = nullptr; /* per bucket: last batch, list, run */
     uint32_t epoch = 0;
     uint32_t last_nparts = 1;             /* buckets of the previous batch (1: count the next one speculatively) */
@@ -2931,13 +2932,12 @@ extern "C" int hm_stream_cells(hm_stream* s, int64_t* cells, int64_t* capacity, 
     return HM_OK;
 }
 
-extern "C" int hm_stream_rollup(hm_stream* s, int span, int merge_groups, int64_t select, uint64_t* keys_out,
-                                uint64_t* counts_out, uint32_t* groups_out, uint32_t* periods_out, int64_t capacity,
-                                int64_t* n_out)
+/* a rollup's three passes: relabel, merge, emit (span: HM_SPAN_*, or
+ * HMS_SPAN_WINDOW with the hour offsets [lo, hi)) */
+static int stream_rollup(hm_stream* s, int span, int merge_groups, int64_t select, uint32_t lo, uint32_t hi,
+                         uint64_t* keys_out, uint64_t* counts_out, uint32_t* groups_out, uint32_t* periods_out,
+                         int64_t capacity, int64_t* n_out)
 {
-    if (!s || !n_out || span < HM_SPAN_HOUR || span > HM_SPAN_ALLTIME || select < -1 || capacity < 0 ||
-        (capacity > 0 && (!keys_out || !counts_out)))
-        return HM_E_ARG;
     *n_out = 0;
     hm_ctx* ctx = s->ctx;
     HIPCHK(hipSetDevice(ctx->device));
@@ -2959,6 +2959,8 @@ extern "C" int hm_stream_rollup(hm_stream* s, int span, int merge_groups, int64_
     a.merge = merge_groups ? 1 : 0;
     a.base = s->base;
     a.select = select;
+    a.lo = lo;
+    a.hi = hi;
     a.keys_out = (uint64_t*)s->rk.p;
     a.counts_out = (uint64_t*)s->rc.p;
     a.cursor = cur;
@@ -2995,6 +2997,113 @@ extern "C" int hm_stream_rollup(hm_stream* s, int span, int merge_groups, int64_
     return HM_OK;
 }
 
+extern "C" int hm_stream_rollup(hm_stream* s, int span, int merge_groups, int64_t select, uint64_t* keys_out,
+                                uint64_t* counts_out, uint32_t* groups_out, uint32_t* periods_out, int64_t capacity,
+                                int64_t* n_out)
+{
+    if (!s || !n_out || span < HM_SPAN_HOUR || span > HM_SPAN_ALLTIME || select < -1 || capacity < 0 ||
+        (capacity > 0 && (!keys_out || !counts_out)))
+        return HM_E_ARG;
+    return stream_rollup(s, span, merge_groups, select, 0, 0, keys_out, counts_out, groups_out, periods_out, capacity,
+                         n_out);
+}
+
+/* hour -> offset from the stream's base, clamped to [0, 2^28] */
+static uint32_t stream_hour_offset(const hm_stream* s, int64_t hour)
+{
+    const int64_t off = hour - (int64_t)s->base;
+    return (uint32_t)std::min<int64_t>(std::max<int64_t>(off, 0), (int64_t)HMS_MAX_HOUR_OFFSET);
+}
+
+extern "C" int hm_stream_window(hm_stream* s, int64_t hour_lo, int64_t hour_hi, int merge_groups, uint64_t* keys_out,
+                                uint64_t* counts_out, uint32_t* groups_out, int64_t capacity, int64_t* n_out)
+{
+    if (!s || !n_out || hour_hi <= hour_lo || capacity < 0 || (capacity > 0 && (!keys_out || !counts_out)))
+        return HM_E_ARG;
+    *n_out = 0;
+    const uint32_t lo = stream_hour_offset(s, hour_lo), hi = stream_hour_offset(s, hour_hi);
+    if (lo >= hi) return HM_OK;   /* all of it outside the stream's hours */
+    return stream_rollup(s, HMS_SPAN_WINDOW, merge_groups, -1, lo, hi, keys_out, counts_out, groups_out, nullptr,
+                         capacity, n_out);
+}
+
+extern "C" int hm_stream_expire(hm_stream* s, int64_t before_hour, int64_t* cells_dropped, int64_t* buckets_freed)
+{
+    if (!s) return HM_E_ARG;
+    if (cells_dropped) *cells_dropped = 0;
+    if (buckets_freed) *buckets_freed = 0;
+    const uint32_t cut = stream_hour_offset(s, before_hour);
+    if (cut == 0 || s->llen == 0) return HM_OK;   /* nothing is dated before the base hour */
+    hm_ctx* ctx = s->ctx;
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t q = ctx->stream;
+    int st;
+    premap_join(s);
+    const uint64_t nb = s->bk.mask + 1;
+    if (!s->akeys && (st = stream_alloc2(s, s->lcap, &s->akeys, &s->acounts))) return st;
+    if (!s->bk_alt && hipMalloc((void**)&s->bk_alt, nb * 8) != hipSuccess) {
+        (void)hipGetLastError();
+        s->bk_alt = nullptr;
+        return HM_E_NOMEM;
+    }
+    /* the survivors' buckets are counted into BUCKETS and listed (NLIST):
+     * the stream's own count comes back if nothing turns out to expire */
+    const uint64_t old_buckets = s->nbuckets;
+    unsigned long long* init = s->hstate + HMS_ST_COUNT;
+    for (int j = 0; j < HMS_ST_COUNT; j++) init[j] = 0;
+    /* CURSOR, BUCKETS, BFULL, EXOTIC, BMM, NLIST in one copy */
+    HIPCHK(hipMemcpyAsync(s->state + HMS_ST_CURSOR, init, (HMS_ST_NLIST - HMS_ST_CURSOR + 1) * 8,
+                          hipMemcpyHostToDevice, q));
+    hm_launch_stream_fill(q, s->bk_alt, nb, HMS_EMPTY);
+    HmsExpireArgs a;
+    a.keys = s->lkeys;
+    a.counts = s->lcounts;
+    a.n = s->llen;
+    a.old_buckets = s->bk;
+    a.new_buckets.keys = s->bk_alt;
+    a.new_buckets.mask = s->bk.mask;
+    a.cb = s->cb;
+    a.cut = cut;
+    a.keys_out = s->akeys;
+    a.counts_out = s->acounts;
+    a.cursor = s->state + HMS_ST_CURSOR;
+    a.state = s->state;
+    hm_launch_stream_expire(q, a);
+    hm_launch_stream_occupied(q, a.new_buckets, s->blist, s->state + HMS_ST_NLIST);
+    HIPCHK(hipGetLastError());
+    /* log_buckets holds old slot ids: it is rebuilt from the new table's
+     * occupied slots, read back as a list (every one has cells in the log;
+     * there are no more of them than the old table's buckets) */
+    std::vector<uint32_t> slots((size_t)std::min<uint64_t>(old_buckets, nb));
+    if (!slots.empty())
+        HIPCHK(hipMemcpyAsync(slots.data(), s->blist, slots.size() * 4, hipMemcpyDeviceToHost, q));
+    st = stream_sync_state(s);
+    const uint64_t kept = s->hstate[HMS_ST_CURSOR], nslots = s->hstate[HMS_ST_NLIST];
+    const bool bad = st || s->hstate[HMS_ST_BFULL] || kept > s->llen || nslots != s->nbuckets || nslots > slots.size();
+    if (bad || kept == s->llen) {
+        /* nothing expired (or, cannot happen, the pass failed): the stream stays as it is */
+        s->nbuckets = old_buckets;
+        init[0] = old_buckets;
+        HIPCHK(hipMemcpyAsync(s->state + HMS_ST_BUCKETS, init, 8, hipMemcpyHostToDevice, q));
+        HIPCHK(hm_sync(q));
+        return st ? st : (bad ? HM_E_HIP : HM_OK);
+    }
+    std::swap(s->lkeys, s->akeys);
+    std::swap(s->lcounts, s->acounts);
+    std::swap(s->bk.keys, s->bk_alt);
+    if (cells_dropped) *cells_dropped = (int64_t)(s->llen - kept);
+    if (buckets_freed) *buckets_freed = (int64_t)(old_buckets - s->nbuckets);
+    s->llen = kept;
+    /* a filter of distinct keys stays distinct: a compact log stays compact */
+    if (kept == 0) s->compact = true;
+    s->log_buckets.clear();
+    s->log_buckets.insert(slots.begin(), slots.begin() + (size_t)nslots);
+    /* slot ids changed: no bucket is flagged by an earlier batch */
+    HIPCHK(hipMemsetAsync(s->bflag, 0, nb * 4, q));
+    s->last_nparts = 1;
+    return HM_OK;
+}
+
 extern "C" int hm_stream_extract(hm_stream* s, int64_t hour, uint64_t* keys_out, uint64_t* counts_out,
                                  uint32_t* hours_out, int64_t capacity, int64_t* n_out)
 {
@@ -3013,9 +3122,9 @@ extern "C" int hm_stream_destroy(hm_stream* s)
     premap_join(s);
     if (s->ctx) (void)hipSetDevice(s->ctx->device);
     if (s->ctx && s->ctx->stream) (void)hipStreamSynchronize(s->ctx->stream);
-    for (void* p : {(void*)s->state, (void*)s->bk.keys, (void*)s->bflag, (void*)s->blist, (void*)s->bloc, s->bids.p,
-                    s->rec.p, s->plat.p, s->plon.p, s->pkeep.p, s->pstart.p, s->pcnt.p, s->rk.p, s->rc.p, s->mk.p,
-                    s->mc.p})
+    for (void* p : {(void*)s->state, (void*)s->bk.keys, (void*)s->bk_alt, (void*)s->bflag, (void*)s->blist,
+                    (void*)s->bloc, s->bids.p, s->rec.p, s->plat.p, s->plon.p, s->pkeep.p, s->pstart.p, s->pcnt.p,
+                    s->rk.p, s->rc.p, s->mk.p, s->mc.p})
         if (p) (void)hipFree(p);
     for (void* p : {(void*)s->lkeys, (void*)s->lcounts, (void*)s->akeys, (void*)s->acounts}) log_free(s, p);
     if (s->hstate) (void)hipHostFree(s->hstate);

@@ -551,6 +551,8 @@ enum {
 #define HMS_TYPE_MONTH 2u
 #define HMS_TYPE_YEAR 3u
 #define HMS_TYPE_ALLTIME 4u
+#define HMS_TYPE_WINDOW 6u               /* (5 is HMS_UNDATED's) one label per group serves every window */
+#define HMS_SPAN_WINDOW 5                /* internal span (after HM_SPAN_ALLTIME): hour offsets [lo, hi) */
 #define HMS_SKIP 0xFFFFFFFFu
 #define HMS_NO_BUCKET 0xFFFFFFFFu
 struct HmsTable {
@@ -598,10 +600,26 @@ struct HmsRelabelArgs {
     int cb, span, merge;
     uint32_t base;
     int64_t select;          /* -1, or the one period value kept */
+    uint32_t lo, hi;         /* HMS_SPAN_WINDOW: hour offsets from base, lo <= hour - base < hi */
     uint64_t* keys_out;      /* label bucket << cb | cell */
     uint64_t* counts_out;
     unsigned long long* cursor;   /* cells written */
     unsigned long long* state;
+};
+/* retention: the log's cells of hours >= cut (and the undated ones), re-keyed
+ * to the buckets of a fresh table (k_stream_expire) */
+struct HmsExpireArgs {
+    const uint64_t* keys;    /* the log */
+    const uint64_t* counts;
+    uint64_t n;
+    HmsBuckets old_buckets;
+    HmsBuckets new_buckets;  /* same capacity, empty */
+    int cb;
+    uint32_t cut;            /* hour offset from base: dated buckets below it are dropped */
+    uint64_t* keys_out;      /* new bucket << cb | cell */
+    uint64_t* counts_out;
+    unsigned long long* cursor;   /* cells kept */
+    unsigned long long* state;    /* HMS_ST_BUCKETS: slots claimed in new_buckets */
 };
 /* merged label cells -> caller's arrays (k_stream_emit) */
 struct HmsEmitArgs {
@@ -634,6 +652,9 @@ void hm_launch_stream_init(hipStream_t s, const HmsTable& t);
 void hm_launch_stream_fill(hipStream_t s, uint64_t* p, uint64_t n, uint64_t v);
 void hm_launch_stream_relabel(hipStream_t s, const HmsRelabelArgs& a);
 void hm_launch_stream_emit(hipStream_t s, const HmsEmitArgs& a);
+void hm_launch_stream_expire(hipStream_t s, const HmsExpireArgs& a);
+/* the occupied slots of a bucket table -> list, their number added to *n */
+void hm_launch_stream_occupied(hipStream_t s, const HmsBuckets& b, uint32_t* list, unsigned long long* n);
 
 /* general count path (hm_general.hip): sort of 128-bit cell keys + zoom cascade */
 struct HmGenArgs {

@@ -25,6 +25,11 @@
  * groups, label) buckets (k_stream_relabel), sum equal keys with the bucketed
  * LDS merge (hm_cells_merge) and list them (k_stream_emit).  The log is
  * compacted (the same merge) when it fills up or its exact size is asked for.
+ * A sliding window (hm_stream_window: the hours [lo, hi)) is one more relabel
+ * rule on the same chain.  Retention (hm_stream_expire, k_stream_expire)
+ * filters the log into the alternate arrays and moves the surviving buckets
+ * to a fresh bucket table, which frees the slots of the expired hours and of
+ * every rollup label.
  */
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -364,7 +369,7 @@ __device__ __forceinline__ uint32_t hms_period_value(uint32_t pw, uint32_t base)
 {
     const uint32_t type = pw >> 28;
     if (type == 0) return base + pw;
-    if (type == HMS_TYPE_ALLTIME) return 0;
+    if (type == HMS_TYPE_ALLTIME || type == HMS_TYPE_WINDOW) return 0;
     return pw & 0x0FFFFFFFu;
 }
 
@@ -375,7 +380,11 @@ __device__ __forceinline__ uint64_t hms_relabel_key(const HmsRelabelArgs& a, uin
     const uint64_t bk = a.buckets.keys[k >> a.cb];
     const uint32_t pw = (uint32_t)bk;
     if ((pw >> 28) != 0 && pw != HMS_UNDATED) return ~0ull;   /* not a raw bucket (cannot happen) */
-    const uint32_t lp = hms_label(pw, a.base, a.span);
+    /* a window: the dated hours [lo, hi) under one label per group (the label
+     * is the scratch merge's id only, it does not carry the bounds) */
+    const uint32_t lp = a.span == HMS_SPAN_WINDOW
+                            ? ((pw != HMS_UNDATED && pw >= a.lo && pw < a.hi) ? HMS_TYPE_WINDOW << 28 : HMS_SKIP)
+                            : hms_label(pw, a.base, a.span);
     if (lp == HMS_SKIP) return ~0ull;
     if (a.select >= 0 && (int64_t)hms_period_value(lp, a.base) != a.select) return ~0ull;
     const uint32_t g = a.merge ? HMS_ALLGROUPS : (uint32_t)(bk >> 32);
@@ -450,6 +459,134 @@ __global__ __launch_bounds__(256) void k_stream_emit(HmsEmitArgs a)
         a.counts_out[j] = a.counts[j];
         if (a.groups_out) a.groups_out[j] = (uint32_t)(bk >> 32);
         if (a.periods_out) a.periods_out[j] = hms_period_value((uint32_t)bk, a.base);
+    }
+}
+
+/* old-table bucket key of a log cell when it outlives the cut (undated cells
+ * have no time and always do), or ~0 */
+__device__ __forceinline__ uint64_t hms_survivor_key(const HmsExpireArgs& a, uint64_t k)
+{
+    const uint64_t bk = a.old_buckets.keys[k >> a.cb];
+    const uint32_t pw = (uint32_t)bk;
+    return (pw == HMS_UNDATED || pw >= a.cut) ? bk : ~0ull;
+}
+
+/* Retention: one pass over the log that filters and re-keys at once.  The
+ * cells that outlive the cut are compacted into the alternate arrays (the
+ * block shape of k_stream_relabel: count per chunk, scan, one reservation
+ * atomic, write) under the bucket their (group, period) key gets in a FRESH
+ * table, so the slots of expired hours, and of every rollup label, are free
+ * again afterwards.  Distinct keys stay distinct (the key -> new bucket map is
+ * one to one), in any order.  A thread takes its HMS_RL_PPT cells HMS_EX_U at a time: the
+ * keys' loads are issued together, then their bucket-key lookups (the pass is
+ * two dependent loads per cell, so one cell at a time it runs at their
+ * latency). */
+#define HMS_EX_U 8
+__global__ __launch_bounds__(256) void k_stream_expire(HmsExpireArgs a)
+{
+    __shared__ uint32_t scr[256 / 64 + 1];
+    __shared__ unsigned long long sbase;
+    const int tid = threadIdx.x;
+    const uint64_t cmask = (1ull << a.cb) - 1ull;
+    uint32_t bclaimed = 0, full = 0;
+    uint64_t wk = HMS_EMPTY;          /* the wave's last shared key and its new bucket */
+    uint32_t wb = HMS_NO_BUCKET;
+    constexpr uint64_t CH = 256 * HMS_RL_PPT;
+    for (uint64_t c0 = (uint64_t)blockIdx.x * CH; c0 < a.n; c0 += (uint64_t)gridDim.x * CH) {
+        uint32_t cnt = 0;
+        for (int j0 = 0; j0 < HMS_RL_PPT; j0 += HMS_EX_U) {
+            uint64_t k[HMS_EX_U];
+#pragma unroll
+            for (int u = 0; u < HMS_EX_U; u++) {
+                const uint64_t i = c0 + (uint64_t)(j0 + u) * 256 + tid;
+                k[u] = i < a.n ? a.keys[i] : 0ull;
+            }
+#pragma unroll
+            for (int u = 0; u < HMS_EX_U; u++) {
+                const uint64_t i = c0 + (uint64_t)(j0 + u) * 256 + tid;
+                if (i < a.n) cnt += hms_survivor_key(a, k[u]) != ~0ull;
+            }
+        }
+        uint32_t tot;
+        const uint32_t pos = hm_block_excl_scan<256>(cnt, scr, &tot);
+        if (tid == 0) sbase = tot ? atomicAdd(a.cursor, (unsigned long long)tot) : 0ull;
+        __syncthreads();
+        /* a wave's survivors go out cell row by cell row (the lanes of one
+         * load, ranked by ballot), so its stores are contiguous */
+        uint64_t wq = sbase + __shfl(pos, 0, 64);
+        __syncthreads();
+        if (!tot) continue;
+        for (int j0 = 0; j0 < HMS_RL_PPT; j0 += HMS_EX_U) {
+            uint64_t k[HMS_EX_U], bk[HMS_EX_U], cn[HMS_EX_U];
+#pragma unroll
+            for (int u = 0; u < HMS_EX_U; u++) {
+                const uint64_t i = c0 + (uint64_t)(j0 + u) * 256 + tid;
+                k[u] = i < a.n ? a.keys[i] : 0ull;
+            }
+#pragma unroll
+            for (int u = 0; u < HMS_EX_U; u++) {
+                const uint64_t i = c0 + (uint64_t)(j0 + u) * 256 + tid;
+                bk[u] = i < a.n ? hms_survivor_key(a, k[u]) : ~0ull;
+            }
+#pragma unroll
+            for (int u = 0; u < HMS_EX_U; u++) {
+                const uint64_t i = c0 + (uint64_t)(j0 + u) * 256 + tid;
+                cn[u] = bk[u] != ~0ull ? a.counts[i] : 0ull;
+            }
+#pragma unroll
+            for (int u = 0; u < HMS_EX_U; u++) {
+                const bool in = bk[u] != ~0ull;
+                const uint64_t inb = __ballot(in);
+                const uint64_t k0 = ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(bk[u] >> 32)) << 32) |
+                                    __builtin_amdgcn_readfirstlane((uint32_t)bk[u]);
+                const bool same = in & (bk[u] == k0);
+                const uint64_t sm = __ballot(same);
+                /* lane 0's key, interned once for the lanes that share it and
+                 * remembered (wave-uniform): the log is in batch order, so runs
+                 * of cells share a bucket and cost no probe at all */
+                if (sm && k0 != wk) {
+                    uint32_t b0 = 0;
+                    if (hm_lane() == 0) b0 = hms_intern(a.new_buckets, k0, &bclaimed);   /* lane 0 is in the group */
+                    wb = __shfl(b0, 0, 64);
+                    wk = k0;
+                }
+                uint32_t b = wb;
+                if (in && !same) b = hms_intern(a.new_buckets, bk[u], &bclaimed);
+                if (in) {
+                    full |= b == HMS_NO_BUCKET;   /* cannot happen: no more keys than the old table held */
+                    const uint64_t q = wq + hm_mbcnt(inb);
+                    a.keys_out[q] = ((uint64_t)(b == HMS_NO_BUCKET ? 0u : b) << a.cb) | (k[u] & cmask);
+                    a.counts_out[q] = cn[u];
+                }
+                wq += (uint64_t)__popcll(inb);
+            }
+        }
+    }
+    uint64_t v[2] = {bclaimed, full};
+    hms_block_sums(v);
+    if (tid == 0) {
+        if (v[0]) atomicAdd(&a.state[HMS_ST_BUCKETS], (unsigned long long)v[0]);
+        if (v[1]) atomicAdd(&a.state[HMS_ST_BFULL], (unsigned long long)v[1]);
+    }
+}
+
+/* the occupied slots of a bucket table, listed (one atomic per wave that
+ * finds any) */
+__global__ __launch_bounds__(256) void k_stream_occupied(HmsBuckets b, uint32_t* __restrict__ list,
+                                                         unsigned long long* n)
+{
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t nb = b.mask + 1;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i0 = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) & ~63ull; i0 < nb; i0 += stride) {
+        const uint64_t i = i0 + lane;
+        const bool m = i < nb && b.keys[i] != HMS_EMPTY;
+        const uint64_t bal = __ballot(m);
+        if (!bal) continue;
+        unsigned long long first = 0;
+        if (lane == 0) first = atomicAdd(n, (unsigned long long)__popcll(bal));
+        first = __shfl(first, 0, 64);
+        if (m) list[first + hm_mbcnt(bal)] = (uint32_t)i;
     }
 }
 
@@ -551,4 +688,17 @@ void hm_launch_stream_relabel(hipStream_t s, const HmsRelabelArgs& a)
 void hm_launch_stream_emit(hipStream_t s, const HmsEmitArgs& a)
 {
     if (a.n) hipLaunchKernelGGL(k_stream_emit, hms_grid(a.n), dim3(256), 0, s, a);
+}
+
+void hm_launch_stream_expire(hipStream_t s, const HmsExpireArgs& a)
+{
+    const uint64_t chunks = (a.n + 256 * HMS_RL_PPT - 1) / (256 * HMS_RL_PPT);
+    if (a.n) hipLaunchKernelGGL(k_stream_expire, dim3((unsigned)(chunks < 1024 ? chunks : 1024)), dim3(256), 0, s, a);
+}
+
+void hm_launch_stream_occupied(hipStream_t s, const HmsBuckets& b, uint32_t* list, unsigned long long* n)
+{
+    uint64_t g = (b.mask + 1 + 4095) / 4096;
+    if (g > 1024) g = 1024;
+    hipLaunchKernelGGL(k_stream_occupied, dim3((unsigned)(g ? g : 1)), dim3(256), 0, s, b, list, n);
 }

@@ -10,6 +10,12 @@ batch (however many hours and groups it holds) and folds its cells in.  Every
 label is a device rollup of the hour buckets:
 
   counts(ALLTIME) / hourly()   per-cell counts of every kept point so far
+  window(lo, hi)               the same cells summed over the epoch hours
+                               lo <= hour < hi (a sliding window such as the
+                               last 24 hours; undated points are in none), and
+                               window_rows(lo, hi, label) their rows
+  expire(before_hour)          retention: the cells of hours < before_hour
+                               leave the stream, their buckets are freed
   rows(timespan)               build_heatmaps' rows, {id: {bin: count}}, for
                                'alltime', 'year', 'month' or 'day' (UTC dates
                                of the epoch hours), with the reference's user
@@ -76,6 +82,27 @@ def _period(timespan: str, hour: np.ndarray) -> np.ndarray:
     m = np.where(mp < 10, mp + 3, mp - 9)
     y = yoe + era * 400 + (m <= 2)
     return y * 12 + m - 1 if timespan == "month" else y
+
+
+def _window_records(x: np.ndarray, hour_lo: int, hour_hi: int, merge_groups: bool) -> np.ndarray:
+    """The out-of-square records x (group, hour or UNDATED_HOUR, zoom, row,
+    col, count) of a window: the dated ones with hour_lo <= hour < hour_hi,
+    summed per (group, zoom, row, col), or over every group (ALLGROUPS)."""
+    h = x[:, 1]
+    x = x[(h != UNDATED_HOUR) & (h >= hour_lo) & (h < hour_hi)]
+    rec = x[:, [0, 2, 3, 4, 5]].copy()
+    if merge_groups:
+        rec[:, 0] = ALLGROUPS
+    return _sum_records(rec, 4)
+
+
+def _expire_records(x: np.ndarray, before_hour: int):
+    """(the records that outlive expire(before_hour), how many are dropped):
+    dated records of an hour < before_hour go, undated ones have no time and
+    stay."""
+    h = x[:, 1]
+    gone = (h != UNDATED_HOUR) & (h < before_hour)
+    return x[~gone], int(gone.sum())
 
 
 def span_label(timespan: str, period: int) -> str:
@@ -319,9 +346,14 @@ class StreamingHeatmap:
         n, k, c, _, p = self.rollup_device("hour", True, -1 if hour == EACH_HOUR else int(hour))
         return n, k, c, (p if hour == EACH_HOUR else None)
 
-    def counts(self, hour: int = ALLTIME) -> device.Counts:
-        """Cells of every kept point (ALLTIME) or of one epoch hour (cells
-        outside the square included)."""
+    def counts(self, hour: int = ALLTIME, window=None) -> device.Counts:
+        """Cells of every kept point (ALLTIME), of one epoch hour, or of the
+        hours window = (lo, hi), lo <= hour < hi (cells outside the square
+        included)."""
+        if window is not None:
+            if hour != ALLTIME:
+                raise ValueError("pass hour or window, not both")
+            return self.window_counts(*window)
         n, keys, counts, _ = self.extract_device(hour)
         z, r, c = device.decode_keys(keys[:n].cpu().numpy().view(np.uint64))
         cnt = counts[:n].cpu().numpy()
@@ -331,6 +363,65 @@ class StreamingHeatmap:
             z, r, c, cnt = (np.concatenate([z, xz.astype(z.dtype)]), np.concatenate([r, xr]),
                             np.concatenate([c, xc]), np.concatenate([cnt, xn]))
         return device.Counts(z, r, c, cnt, 0, [])
+
+    # ------------------------------------------------- windows and retention
+
+    def window_device(self, hour_lo: int, hour_hi: int, merge_groups: bool = True):
+        """(n, keys, counts, groups) as torch CUDA tensors: the cells of the
+        dated hours hour_lo <= hour < hour_hi summed per group, or over every
+        group (hm_stream_window; out-of-square cells not included)."""
+        torch = self._torch
+        self.ctx.bind_stream()
+        if int(hour_hi) <= int(hour_lo):
+            raise ValueError("a window needs hour_lo < hour_hi (got %d, %d)" % (hour_lo, hour_hi))
+        # sized as rollup_device does: from the last window of this width
+        memo = self.__dict__.setdefault("_rollup_n", {})
+        mk = ("window", bool(merge_groups), int(hour_hi) - int(hour_lo))
+        cap = min(max(1024, self._log_capacity()), max(1024, int(memo.get(mk, 1 << 20) * 1.25) + 1024))
+        dev = "cuda:%d" % self.device_index
+        while True:
+            keys = torch.empty(cap, dtype=torch.int64, device=dev)
+            counts = torch.empty(cap, dtype=torch.int64, device=dev)
+            groups = torch.empty(cap, dtype=torch.int32, device=dev)
+            n = ctypes.c_int64(0)
+            rc = self.ctx.L.hm_stream_window(self.ptr, int(hour_lo), int(hour_hi), int(bool(merge_groups)),
+                                             device._ptr(keys), device._ptr(counts), device._ptr(groups), cap,
+                                             ctypes.byref(n))
+            if rc == _lib.HM_E_CAPACITY and n.value > cap:
+                cap = n.value + 1024
+                continue
+            if rc != _lib.HM_OK:
+                _lib.raise_for(rc)
+            memo[mk] = n.value
+            return n.value, keys, counts, groups
+
+    def window(self, hour_lo: int, hour_hi: int, merge_groups: bool = True):
+        """Host arrays (group u32, zoom, row, col, count) of the window, cells
+        outside the square included."""
+        n, keys, counts, groups = self.window_device(hour_lo, hour_hi, merge_groups)
+        z, r, c = device.decode_keys(keys[:n].cpu().numpy().view(np.uint64))
+        out = (groups[:n].cpu().numpy().view(np.uint32), z, r, c, counts[:n].cpu().numpy())
+        if not len(self._x):
+            return out
+        x = _window_records(self._x, int(hour_lo), int(hour_hi), merge_groups)
+        return tuple(np.concatenate([a, x[:, j].astype(a.dtype)]) for j, a in enumerate(out))
+
+    def window_counts(self, hour_lo: int, hour_hi: int) -> device.Counts:
+        """Cells of every kept point of the hours hour_lo <= hour < hour_hi."""
+        _, z, r, c, cnt = self.window(hour_lo, hour_hi, True)
+        return device.Counts(z, r, c, cnt, 0, [])
+
+    def expire(self, before_hour: int):
+        """Retention: drop the cells of every hour < before_hour (undated
+        points stay) and free their buckets and every rollup label's.
+        Returns (cells dropped, bucket slots freed)."""
+        self.ctx.bind_stream()
+        a, b = ctypes.c_int64(0), ctypes.c_int64(0)
+        rc = self.ctx.L.hm_stream_expire(self.ptr, int(before_hour), ctypes.byref(a), ctypes.byref(b))
+        if rc != _lib.HM_OK:
+            _lib.raise_for(rc)
+        self._x, gone = _expire_records(self._x, int(before_hour))
+        return a.value + gone, b.value
 
     def hourly(self):
         """{epoch hour: Counts} for every non-empty hour."""
@@ -364,6 +455,36 @@ class StreamingHeatmap:
                                            (gg[q].astype(np.int64), gz[q], gr[q], gc[q], gn[q]), mz + d, d,
                                            span_label(timespan, p)))
         return _hm.concat_cells(parts, self.labels, d)
+
+    def window_cells(self, hour_lo: int, hour_hi: int, label: str, max_zoom_level=None, delta=None) -> "_hm.Cells":
+        """The bins of build_heatmaps' rows over the window's points, under
+        the caller's timespan label (e.g. 'last24h': the reference has none
+        for a window)."""
+        d = _hm.DETAIL_ZOOM_DELTA if delta is None else int(delta)
+        mz = self.zmax - d if max_zoom_level is None else int(max_zoom_level)
+        if mz + d != self.zmax or self.zmin > d + 1:
+            raise ValueError("rows need zooms %d..%d; the stream holds %d..%d" % (d + 1, mz + d, self.zmin, self.zmax))
+        if not isinstance(label, str) or _hm.KEY_SEPERATOR in label:
+            raise ValueError("window label %r must be a string without the key separator %r"
+                             % (label, _hm.KEY_SEPERATOR))
+        if self._explicit_max >= len(self.labels):
+            raise ValueError("rows need a label per group: group id %d was passed as group= and has none "
+                             "(feed the stream with user_id= to build rows)" % self._explicit_max)
+        _, az, ar, ac, an = self.window(hour_lo, hour_hi, merge_groups=True)
+        gg, gz, gr, gc, gn = self.window(hour_lo, hour_hi, merge_groups=False)
+        q = gg != NOGROUP
+        return _hm.combine_cells(self.labels, (az, ar, ac, an), (gg[q].astype(np.int64), gz[q], gr[q], gc[q], gn[q]),
+                                 mz + d, d, label)
+
+    def window_rows(self, hour_lo: int, hour_hi: int, label: str, max_zoom_level=None, delta=None) -> dict:
+        """{row_id: {bin_id: float}} as build_heatmaps would give over the
+        points of the hours hour_lo <= hour < hour_hi, row ids
+        '<group>|<label>|<tile>'."""
+        return _hm.cells_to_rows(self.window_cells(hour_lo, hour_hi, label, max_zoom_level, delta))
+
+    def window_table(self, hour_lo: int, hour_hi: int, label: str, max_zoom_level=None, delta=None):
+        """The same rows as a pyarrow Table(id, heatmap JSON)."""
+        return _hm.cells_to_table(self.window_cells(hour_lo, hour_hi, label, max_zoom_level, delta))
 
     def rows(self, timespan: str = "alltime", max_zoom_level=None, delta=None) -> dict:
         """{row_id: {bin_id: float}} as build_heatmaps would give over every

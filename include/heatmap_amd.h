@@ -242,7 +242,25 @@ int hm_last_stats(hm_ctx* ctx, int64_t* slow_points, double* stage_us, int n_sta
  *                     with *n_out = cells needed when capacity is too small.
  *   hm_stream_extract hour = HM_STREAM_ALLTIME, HM_STREAM_EACH_HOUR (hours_out
  *                     receives each cell's hour) or one epoch hour, summed
- *                     over groups (a rollup). */
+ *                     over groups (a rollup).
+ *   hm_stream_window  a sliding window: the cells of every dated hour with
+ *                     hour_lo <= hour < hour_hi summed per group, or over every
+ *                     group (merge_groups: group = 0xFFFFFFFF), through the
+ *                     rollup's passes.  Undated cells are in no window.  Bounds
+ *                     outside [base_hour, base_hour + 2^28) are clamped; a
+ *                     window without data is HM_OK with *n_out = 0; hour_hi <=
+ *                     hour_lo is HM_E_ARG.  groups_out may be NULL.  Keys and
+ *                     HM_E_CAPACITY as hm_stream_rollup.
+ *   hm_stream_expire  retention: drops every cell of a dated hour < before_hour
+ *                     (undated cells have no time and stay) in one pass over the
+ *                     log, and moves the surviving (group, hour) buckets to a
+ *                     fresh table: *cells_dropped cells left the log and
+ *                     *buckets_freed bucket slots (those of the expired hours
+ *                     and of every rollup label interned so far) are free
+ *                     again (either may be NULL).  before_hour <= base_hour, or
+ *                     a cut below which the log holds nothing, changes nothing
+ *                     and gives (0, 0).  A later batch may bring an expired hour
+ *                     back.  Enqueued after all pending work; waits once. */
 #define HM_STREAM_ALLTIME (-1)
 #define HM_STREAM_EACH_HOUR (-2)
 #define HM_STREAM_MAX_HOURS (1 << 28)
@@ -264,6 +282,9 @@ int hm_stream_rollup(hm_stream* s, int span, int merge_groups, int64_t select, u
                      int64_t* n_out);
 int hm_stream_extract(hm_stream* s, int64_t hour, uint64_t* keys_out, uint64_t* counts_out, uint32_t* hours_out,
                       int64_t capacity, int64_t* n_out);
+int hm_stream_window(hm_stream* s, int64_t hour_lo, int64_t hour_hi, int merge_groups, uint64_t* keys_out,
+                     uint64_t* counts_out, uint32_t* groups_out, int64_t capacity, int64_t* n_out);
+int hm_stream_expire(hm_stream* s, int64_t before_hour, int64_t* cells_dropped, int64_t* buckets_freed);
 int hm_stream_destroy(hm_stream* s);
 
 /* Multi-GPU exchange of hm_count cells (one process per GPU; the collectives
