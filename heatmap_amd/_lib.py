@@ -29,12 +29,14 @@ HM_CELLS_U64, HM_CELLS_U32, HM_CELLS_REC10, HM_CELLS_G12 = 8, 4, 10, 12   # exch
 HM_COUNT_MAX_ZOOM = 21
 HM_ABI_VERSION = 7
 HM_SPAN_HOUR, HM_SPAN_DAY, HM_SPAN_MONTH, HM_SPAN_YEAR, HM_SPAN_ALLTIME = 0, 1, 2, 3, 4
+HM_STREAM_ALLTIME = -1
+HM_VIEW_MAX_RECTS, HM_VIEW_MERGED, HM_VIEW_EACH = 32, -1, -2   # hm_stream_view
 
 EXPORTS = ["hm_abi_version", "hm_status_string", "hm_ctx_create", "hm_ctx_set_stream", "hm_ctx_destroy", "hm_ctx_tune",
            "hm_project", "hm_project_scalar", "hm_count", "hm_count_tiles", "hm_count_grouped", "hm_count_grouped_tiles",
            "hm_count_grouped_packed", "hm_count_grouped_packed_tiles", "hm_last_error", "hm_last_stats", "hm_synth",
            "hm_stream_create", "hm_stream_add", "hm_stream_cells", "hm_stream_rollup", "hm_stream_extract",
-           "hm_stream_window", "hm_stream_expire", "hm_stream_destroy",
+           "hm_stream_window", "hm_stream_view", "hm_stream_expire", "hm_stream_destroy",
            "hm_dense_grid_size", "hm_cells_route", "hm_cells_merge", "hm_cells_merge_runs",
            "hm_cells_route_pieces", "hm_cells_merge_pieces", "hm_dense_cells", "hm_format_bins", "hm_format_ids", "hm_bench_read"]
 
@@ -110,6 +112,8 @@ def load() -> ctypes.CDLL:
         L.hm_stream_rollup.argtypes = [vp, c.c_int, c.c_int, c.c_int64, vp, vp, vp, vp, c.c_int64, P(c.c_int64)]
         L.hm_stream_extract.argtypes = [vp, c.c_int64, vp, vp, vp, c.c_int64, P(c.c_int64)]
         L.hm_stream_window.argtypes = [vp, c.c_int64, c.c_int64, c.c_int, vp, vp, vp, c.c_int64, P(c.c_int64)]
+        L.hm_stream_view.argtypes = [vp, c.c_int64, c.c_int64, c.c_int64, P(c.c_int64), c.c_int, vp, vp, vp, c.c_int64,
+                                     P(c.c_int64)]
         L.hm_stream_expire.argtypes = [vp, c.c_int64, P(c.c_int64), P(c.c_int64)]
         L.hm_stream_destroy.argtypes = [vp]
         L.hm_dense_grid_size.argtypes = [c.c_int]

@@ -2932,6 +2932,44 @@ extern "C" int hm_stream_cells(hm_stream* s, int64_t* cells, int64_t* capacity, 
     return HM_OK;
 }
 
+/* the tail of every query: the filter pass's read-back, then the label cells
+ * in the scratch arrays (HMS_ST_CURSOR of them) merged and emitted */
+static int stream_merge_emit(hm_stream* s, uint64_t* keys_out, uint64_t* counts_out, uint32_t* groups_out,
+                             uint32_t* periods_out, int64_t capacity, int64_t* n_out)
+{
+    hm_ctx* ctx = s->ctx;
+    hipStream_t q = ctx->stream;
+    int st;
+    if ((st = stream_sync_state(s))) return st;
+    if (s->hstate[HMS_ST_BFULL]) return HM_E_CAPACITY;   /* no bucket left for a rollup label */
+    const uint64_t m = s->hstate[HMS_ST_CURSOR];
+    if (m == 0) return HM_OK;
+    /* equal label cells summed */
+    if ((st = stream_buf(s, s->mk, m * 8)) || (st = stream_buf(s, s->mc, m * 8))) return st;
+    int64_t nd = 0;
+    if ((st = cells_merge(ctx, (const uint64_t*)s->rk.p, (const uint64_t*)s->rc.p, HM_CELLS_U64, (int64_t)m, nullptr, 0,
+                          (uint64_t*)s->mk.p, (uint64_t*)s->mc.p, (int64_t)m, &nd)))
+        return st;
+    *n_out = nd;
+    if (nd > capacity) return HM_E_CAPACITY;
+    HmsEmitArgs e;
+    e.keys = (const uint64_t*)s->mk.p;
+    e.counts = (const uint64_t*)s->mc.p;
+    e.n = (uint64_t)nd;
+    e.buckets = s->bk;
+    e.cb = s->cb;
+    e.zmin = s->zmin;
+    e.zmax = s->zmax;
+    e.base = s->base;
+    e.keys_out = keys_out;
+    e.counts_out = counts_out;
+    e.groups_out = groups_out;
+    e.periods_out = periods_out;
+    hm_launch_stream_emit(q, e);
+    HIPCHK(hipGetLastError());
+    return HM_OK;
+}
+
 /* a rollup's three passes: relabel, merge, emit (span: HM_SPAN_*, or
  * HMS_SPAN_WINDOW with the hour offsets [lo, hi)) */
 static int stream_rollup(hm_stream* s, int span, int merge_groups, int64_t select, uint32_t lo, uint32_t hi,
@@ -2967,34 +3005,7 @@ static int stream_rollup(hm_stream* s, int span, int merge_groups, int64_t selec
     a.state = s->state;
     hm_launch_stream_relabel(q, a);
     HIPCHK(hipGetLastError());
-    if ((st = stream_sync_state(s))) return st;
-    if (s->hstate[HMS_ST_BFULL]) return HM_E_CAPACITY;   /* no bucket left for a rollup label */
-    const uint64_t m = s->hstate[HMS_ST_CURSOR];
-    if (m == 0) return HM_OK;
-    /* equal label cells summed */
-    if ((st = stream_buf(s, s->mk, m * 8)) || (st = stream_buf(s, s->mc, m * 8))) return st;
-    int64_t nd = 0;
-    if ((st = cells_merge(ctx, (const uint64_t*)s->rk.p, (const uint64_t*)s->rc.p, HM_CELLS_U64, (int64_t)m, nullptr, 0,
-                          (uint64_t*)s->mk.p, (uint64_t*)s->mc.p, (int64_t)m, &nd)))
-        return st;
-    *n_out = nd;
-    if (nd > capacity) return HM_E_CAPACITY;
-    HmsEmitArgs e;
-    e.keys = (const uint64_t*)s->mk.p;
-    e.counts = (const uint64_t*)s->mc.p;
-    e.n = (uint64_t)nd;
-    e.buckets = s->bk;
-    e.cb = s->cb;
-    e.zmin = s->zmin;
-    e.zmax = s->zmax;
-    e.base = s->base;
-    e.keys_out = keys_out;
-    e.counts_out = counts_out;
-    e.groups_out = groups_out;
-    e.periods_out = periods_out;
-    hm_launch_stream_emit(q, e);
-    HIPCHK(hipGetLastError());
-    return HM_OK;
+    return stream_merge_emit(s, keys_out, counts_out, groups_out, periods_out, capacity, n_out);
 }
 
 extern "C" int hm_stream_rollup(hm_stream* s, int span, int merge_groups, int64_t select, uint64_t* keys_out,
@@ -3025,6 +3036,79 @@ extern "C" int hm_stream_window(hm_stream* s, int64_t hour_lo, int64_t hour_hi, 
     if (lo >= hi) return HM_OK;   /* all of it outside the stream's hours */
     return stream_rollup(s, HMS_SPAN_WINDOW, merge_groups, -1, lo, hi, keys_out, counts_out, groups_out, nullptr,
                          capacity, n_out);
+}
+
+/* a view's three passes: filter (k_stream_view, in place of the relabel),
+ * then the rollup's merge and emit over the survivors only */
+static int stream_view(hm_stream* s, HmsViewArgs& a, uint64_t* keys_out, uint64_t* counts_out, uint32_t* groups_out,
+                       int64_t capacity, int64_t* n_out)
+{
+    hm_ctx* ctx = s->ctx;
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t q = ctx->stream;
+    int st;
+    if (s->llen == 0) return HM_OK;
+    if ((st = stream_buf(s, s->rk, s->llen * 8)) || (st = stream_buf(s, s->rc, s->llen * 8))) return st;
+    unsigned long long* cur = s->state + HMS_ST_CURSOR;
+    HIPCHK(hipMemsetAsync(cur, 0, 8, q));
+    HIPCHK(hipMemsetAsync(s->state + HMS_ST_BFULL, 0, 8, q));
+    a.keys = s->lkeys;
+    a.counts = s->lcounts;
+    a.n = s->llen;
+    a.buckets = s->bk;
+    a.cb = s->cb;
+    a.keys_out = (uint64_t*)s->rk.p;
+    a.counts_out = (uint64_t*)s->rc.p;
+    a.cursor = cur;
+    a.state = s->state;
+    hm_launch_stream_view(q, a);
+    HIPCHK(hipGetLastError());
+    return stream_merge_emit(s, keys_out, counts_out, groups_out, nullptr, capacity, n_out);
+}
+
+extern "C" int hm_stream_view(hm_stream* s, int64_t hour_lo, int64_t hour_hi, int64_t group, const int64_t* rects,
+                              int nrects, uint64_t* keys_out, uint64_t* counts_out, uint32_t* groups_out,
+                              int64_t capacity, int64_t* n_out)
+{
+    const bool alltime = hour_lo == HM_STREAM_ALLTIME && hour_hi == HM_STREAM_ALLTIME;
+    if (!s || !n_out || !rects || nrects < 1 || nrects > HM_VIEW_MAX_RECTS || (!alltime && hour_hi <= hour_lo) ||
+        group < HM_VIEW_EACH || group > (int64_t)HMS_NOGROUP || capacity < 0 ||
+        (capacity > 0 && (!keys_out || !counts_out)))
+        return HM_E_ARG;
+    *n_out = 0;
+    HmsViewArgs a;
+    a.nrects = 0;
+    uint64_t box_hi = 0;
+    a.box_lo = ~0ull;
+    for (int r = 0; r < nrects; r++) {
+        const int64_t z = rects[5 * r], side = 1ll << (z < 0 || z > HM_MAX_ZOOM ? 0 : z);
+        int64_t rlo = rects[5 * r + 1], rhi = rects[5 * r + 2], clo = rects[5 * r + 3], chi = rects[5 * r + 4];
+        if (z < s->zmin || z > s->zmax || rhi <= rlo || chi <= clo) return HM_E_ARG;
+        /* clipped to the square; what is left may be nothing */
+        rlo = std::max<int64_t>(rlo, 0), clo = std::max<int64_t>(clo, 0);
+        rhi = std::min<int64_t>(rhi, side), chi = std::min<int64_t>(chi, side);
+        if (rhi <= rlo || chi <= clo) continue;
+        HmsViewRect& R = a.rects[a.nrects++];
+        R.id_lo = ((1ull << (2 * z)) - 1ull) / 3ull + ((uint64_t)rlo << z);
+        R.span = (uint64_t)(rhi - rlo) << z;
+        R.cmask = (uint32_t)(side - 1);
+        R.col_lo = (uint32_t)clo;
+        R.col_w = (uint32_t)(chi - clo);
+        R.pad = 0;
+        a.box_lo = std::min(a.box_lo, R.id_lo);
+        box_hi = std::max(box_hi, R.id_lo + R.span);
+    }
+    if (a.nrects == 0) return HM_OK;   /* every rectangle outside the square */
+    a.box_span = box_hi - a.box_lo;
+    a.alltime = alltime ? 1 : 0;
+    a.lo = a.hi = 0;
+    if (!alltime) {
+        a.lo = stream_hour_offset(s, hour_lo), a.hi = stream_hour_offset(s, hour_hi);
+        if (a.lo >= a.hi) return HM_OK;   /* all of it outside the stream's hours */
+    }
+    a.gmode = group == HM_VIEW_MERGED ? HMS_VIEW_MERGED : (group == HM_VIEW_EACH ? HMS_VIEW_EACH : HMS_VIEW_GROUP);
+    a.group = group >= 0 ? (uint32_t)group : 0u;
+    return stream_view(s, a, keys_out, counts_out, groups_out, capacity, n_out);
 }
 
 extern "C" int hm_stream_expire(hm_stream* s, int64_t before_hour, int64_t* cells_dropped, int64_t* buckets_freed)

@@ -621,6 +621,38 @@ struct HmsExpireArgs {
     unsigned long long* cursor;   /* cells kept */
     unsigned long long* state;    /* HMS_ST_BUCKETS: slots claimed in new_buckets */
 };
+/* a viewport query: the log's cells inside any of a few rectangles, of the
+ * window's hours and the wanted group(s), re-keyed to label buckets
+ * (k_stream_view).  A rectangle (zoom z, rows [row_lo, row_hi), cols [col_lo,
+ * col_hi)) is tested on the cell id alone: its rows are the id interval
+ * [id_lo, id_lo + span), id_lo = off(z) + (row_lo << z), and the column is the
+ * low z bits of id - id_lo. */
+#define HMS_VIEW_MAX_RECTS 32
+#define HMS_VIEW_MERGED 0                /* gmode: one label, HMS_ALLGROUPS */
+#define HMS_VIEW_EACH 1                  /* a label per group */
+#define HMS_VIEW_GROUP 2                 /* the cells of `group` only */
+struct HmsViewRect {
+    uint64_t id_lo;
+    uint64_t span;           /* (row_hi - row_lo) << z */
+    uint32_t cmask;          /* 2^z - 1 */
+    uint32_t col_lo, col_w;  /* col_lo <= column < col_lo + col_w */
+    uint32_t pad;
+};
+struct HmsViewArgs {
+    const uint64_t* keys;    /* the log */
+    const uint64_t* counts;
+    uint64_t n;
+    HmsBuckets buckets;
+    int cb, nrects, gmode, alltime;   /* alltime: every raw bucket, the undated ones included */
+    uint32_t lo, hi;         /* else the dated hour offsets lo <= hour - base < hi */
+    uint32_t group;          /* HMS_VIEW_GROUP */
+    uint64_t box_lo, box_span;    /* the id interval that holds every rectangle */
+    uint64_t* keys_out;      /* label bucket << cb | cell */
+    uint64_t* counts_out;
+    unsigned long long* cursor;   /* cells written */
+    unsigned long long* state;
+    HmsViewRect rects[HMS_VIEW_MAX_RECTS];   /* by value: wave-uniform, read as scalars */
+};
 /* merged label cells -> caller's arrays (k_stream_emit) */
 struct HmsEmitArgs {
     const uint64_t* keys;
@@ -652,6 +684,7 @@ void hm_launch_stream_init(hipStream_t s, const HmsTable& t);
 void hm_launch_stream_fill(hipStream_t s, uint64_t* p, uint64_t n, uint64_t v);
 void hm_launch_stream_relabel(hipStream_t s, const HmsRelabelArgs& a);
 void hm_launch_stream_emit(hipStream_t s, const HmsEmitArgs& a);
+void hm_launch_stream_view(hipStream_t s, const HmsViewArgs& a);
 void hm_launch_stream_expire(hipStream_t s, const HmsExpireArgs& a);
 /* the occupied slots of a bucket table -> list, their number added to *n */
 void hm_launch_stream_occupied(hipStream_t s, const HmsBuckets& b, uint32_t* list, unsigned long long* n);

@@ -26,7 +26,10 @@
  * LDS merge (hm_cells_merge) and list them (k_stream_emit).  The log is
  * compacted (the same merge) when it fills up or its exact size is asked for.
  * A sliding window (hm_stream_window: the hours [lo, hi)) is one more relabel
- * rule on the same chain.  Retention (hm_stream_expire, k_stream_expire)
+ * rule on the same chain.  A viewport (hm_stream_view) swaps the relabel for
+ * k_stream_view, which keeps only the cells inside a few rectangles, tested on
+ * the key alone, so merge and emit see the viewport's cells, not the window's.
+ * Retention (hm_stream_expire, k_stream_expire)
  * filters the log into the alternate arrays and moves the surviving buckets
  * to a fresh bucket table, which frees the slots of the expired hours and of
  * every rollup label.
@@ -462,6 +465,114 @@ __global__ __launch_bounds__(256) void k_stream_emit(HmsEmitArgs a)
     }
 }
 
+/* label key of a raw bucket key in a view (the window's or alltime's label,
+ * under the group, HMS_ALLGROUPS or the selected group), or ~0: not in it */
+__device__ __forceinline__ uint64_t hms_view_key(const HmsViewArgs& a, uint64_t bk)
+{
+    const uint32_t pw = (uint32_t)bk, g = (uint32_t)(bk >> 32);
+    const bool dated = (pw >> 28) == 0;
+    const bool in = a.alltime ? (dated || pw == HMS_UNDATED) : (dated && pw >= a.lo && pw < a.hi);
+    if (!in || (a.gmode == HMS_VIEW_GROUP && g != a.group)) return ~0ull;
+    const uint32_t lp = (a.alltime ? HMS_TYPE_ALLTIME : HMS_TYPE_WINDOW) << 28;
+    return ((uint64_t)(a.gmode == HMS_VIEW_MERGED ? HMS_ALLGROUPS : g) << 32) | lp;
+}
+
+/* A viewport query's filter: ONE pass over the log's keys.  A thread takes
+ * HMS_VW_U keys at a time (their loads issued together) and tests each cell id
+ * against the rectangles (HmsViewArgs: a few compares per rectangle on
+ * wave-uniform bounds).  Most cells of a log fail and cost their 8-byte key
+ * and nothing else; a wave none of whose cells lies in the rectangles' common
+ * id interval skips even the rectangle loop.  Only the cells inside a
+ * rectangle read their bucket's key (hour and group tests), only the
+ * survivors their count.  A wave ranks its survivors by ballot and reserves
+ * their room with one atomic per HMS_VW_U rows that hold any (the output
+ * order is unspecified, so nothing is read twice); labels are interned as
+ * k_stream_expire does, once per wave while the label stays the same. */
+#ifndef HMS_VW_U
+#define HMS_VW_U 8
+#endif
+__global__ __launch_bounds__(256) void k_stream_view(HmsViewArgs a)
+{
+    constexpr int U = HMS_VW_U;
+    const int tid = threadIdx.x;
+    const uint32_t lane = (uint32_t)tid & 63u;
+    const uint64_t cmask = (1ull << a.cb) - 1ull;
+    uint32_t bclaimed = 0, full = 0;
+    uint64_t wk = HMS_EMPTY;          /* the wave's last shared label and its bucket */
+    uint32_t wb = HMS_NO_BUCKET;
+    constexpr uint64_t CH = 256 * U;
+    for (uint64_t c0 = (uint64_t)blockIdx.x * CH; c0 < a.n; c0 += (uint64_t)gridDim.x * CH) {
+        uint64_t k[U];
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const uint64_t i = c0 + (uint64_t)u * 256 + tid;
+            k[u] = i < a.n ? a.keys[i] : 0ull;
+        }
+        uint32_t box = 0;             /* bit u: cell u lies in the rectangles' common interval */
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const uint64_t i = c0 + (uint64_t)u * 256 + tid;
+            box |= (uint32_t)(i < a.n && (k[u] & cmask) - a.box_lo < a.box_span) << u;
+        }
+        if (!__ballot(box != 0)) continue;
+        uint32_t hit = 0;             /* bit u: cell u lies in a rectangle */
+        for (int r = 0; r < a.nrects; r++) {
+            const HmsViewRect R = a.rects[r];
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+                const uint64_t d = (k[u] & cmask) - R.id_lo;
+                hit |= (uint32_t)(d < R.span && ((uint32_t)d & R.cmask) - R.col_lo < R.col_w) << u;
+            }
+        }
+        hit &= box;
+        if (!__ballot(hit != 0)) continue;
+        uint64_t lk[U], cn[U], bal[U];
+#pragma unroll
+        for (int u = 0; u < U; u++)
+            lk[u] = (hit >> u) & 1u ? hms_view_key(a, a.buckets.keys[(k[u] >> a.cb) & a.buckets.mask]) : ~0ull;
+        uint32_t tot = 0;
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const uint64_t i = c0 + (uint64_t)u * 256 + tid;
+            cn[u] = lk[u] != ~0ull ? a.counts[i] : 0ull;
+            bal[u] = __ballot(lk[u] != ~0ull);
+            tot += (uint32_t)__popcll(bal[u]);
+        }
+        if (!tot) continue;
+        unsigned long long first = 0;
+        if (lane == 0) first = atomicAdd(a.cursor, (unsigned long long)tot);
+        uint64_t wq = __shfl(first, 0, 64);
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            if (!bal[u]) continue;
+            const bool in = (bal[u] >> lane) & 1ull;
+            const int leader = __ffsll((unsigned long long)bal[u]) - 1;
+            const uint64_t k0 = __shfl((unsigned long long)lk[u], leader, 64);
+            if (k0 != wk) {
+                uint32_t b0 = 0;
+                if ((int)lane == leader) b0 = hms_intern(a.buckets, k0, &bclaimed);
+                wb = __shfl(b0, leader, 64);
+                wk = k0;
+            }
+            uint32_t b = wb;
+            if (in && lk[u] != k0) b = hms_intern(a.buckets, lk[u], &bclaimed);
+            if (in) {
+                full |= b == HMS_NO_BUCKET;   /* the caller discards the view */
+                const uint64_t q = wq + hm_mbcnt(bal[u]);
+                a.keys_out[q] = ((uint64_t)(b == HMS_NO_BUCKET ? 0u : b) << a.cb) | (k[u] & cmask);
+                a.counts_out[q] = cn[u];
+            }
+            wq += (uint64_t)__popcll(bal[u]);
+        }
+    }
+    uint64_t v[2] = {bclaimed, full};
+    hms_block_sums(v);
+    if (tid == 0) {
+        if (v[0]) atomicAdd(&a.state[HMS_ST_BUCKETS], (unsigned long long)v[0]);
+        if (v[1]) atomicAdd(&a.state[HMS_ST_BFULL], (unsigned long long)v[1]);
+    }
+}
+
 /* old-table bucket key of a log cell when it outlives the cut (undated cells
  * have no time and always do), or ~0 */
 __device__ __forceinline__ uint64_t hms_survivor_key(const HmsExpireArgs& a, uint64_t k)
@@ -688,6 +799,12 @@ void hm_launch_stream_relabel(hipStream_t s, const HmsRelabelArgs& a)
 void hm_launch_stream_emit(hipStream_t s, const HmsEmitArgs& a)
 {
     if (a.n) hipLaunchKernelGGL(k_stream_emit, hms_grid(a.n), dim3(256), 0, s, a);
+}
+
+void hm_launch_stream_view(hipStream_t s, const HmsViewArgs& a)
+{
+    const uint64_t chunks = (a.n + 256 * HMS_VW_U - 1) / (256 * HMS_VW_U);
+    if (a.n) hipLaunchKernelGGL(k_stream_view, dim3((unsigned)(chunks < 2048 ? chunks : 2048)), dim3(256), 0, s, a);
 }
 
 void hm_launch_stream_expire(hipStream_t s, const HmsExpireArgs& a)

@@ -14,6 +14,12 @@ label is a device rollup of the hour buckets:
                                lo <= hour < hi (a sliding window such as the
                                last 24 hours; undated points are in none), and
                                window_rows(lo, hi, label) their rows
+  view(rects, hours, group)    only the cells inside the rectangles (zoom, rows,
+                               cols) of a viewport, for a window of hours or
+                               alltime, merged, per group or for one group, and
+                               tile_rows(tiles, hours, label, user) the rows of
+                               the heatmap tiles on screen (hm_stream_view: one
+                               pass over the log's keys)
   expire(before_hour)          retention: the cells of hours < before_hour
                                leave the stream, their buckets are freed
   rows(timespan)               build_heatmaps' rows, {id: {bin: count}}, for
@@ -94,6 +100,40 @@ def _window_records(x: np.ndarray, hour_lo: int, hour_hi: int, merge_groups: boo
     if merge_groups:
         rec[:, 0] = ALLGROUPS
     return _sum_records(rec, 4)
+
+
+def _view_records(x: np.ndarray, rects, hours, group) -> np.ndarray:
+    """The out-of-square records x (group, hour or UNDATED_HOUR, zoom, row,
+    col, count) of a view: those inside any of the (unclipped) rectangles
+    (zoom, row_lo, row_hi, col_lo, col_hi), of hours = None (every record,
+    undated ones included) or (lo, hi) (the dated ones with lo <= hour < hi),
+    and of group = 'merged' (summed over every group: ALLGROUPS), 'each' or
+    one group id.  Returns (group, zoom, row, col, count) records."""
+    g, h, z, r, c = (x[:, j] for j in range(5))
+    m = np.zeros(len(x), dtype=bool)
+    for rz, rlo, rhi, clo, chi in rects:
+        m |= (z == rz) & (r >= rlo) & (r < rhi) & (c >= clo) & (c < chi)
+    if hours is not None:
+        m &= (h != UNDATED_HOUR) & (h >= hours[0]) & (h < hours[1])
+    if group not in ("merged", "each"):
+        m &= g == int(group)
+    rec = x[m][:, [0, 2, 3, 4, 5]].copy()
+    if group == "merged":
+        rec[:, 0] = ALLGROUPS
+    return _sum_records(rec, 4)
+
+
+def tile_rects(tiles, d: int):
+    """The detail-zoom rectangle (zoom, row_lo, row_hi, col_lo, col_hi) of each
+    heatmap row tile (tz, tr, tc): its 2^d x 2^d bins at zoom tz + d."""
+    return [(tz + d, tr << d, (tr + 1) << d, tc << d, (tc + 1) << d) for tz, tr, tc in tiles]
+
+
+def _cells_subset(cells: "_hm.Cells", m: np.ndarray) -> "_hm.Cells":
+    """The bins of cells under the mask m."""
+    return _hm.Cells(cells.labels, np.asarray(cells.label)[m], np.asarray(cells.zoom)[m], np.asarray(cells.row)[m],
+                     np.asarray(cells.col)[m], np.asarray(cells.value)[m], cells.delta, cells.spans, cells.span[m],
+                     tile_override=cells.tile_override)
 
 
 def _expire_records(x: np.ndarray, before_hour: int):
@@ -410,6 +450,156 @@ class StreamingHeatmap:
         """Cells of every kept point of the hours hour_lo <= hour < hour_hi."""
         _, z, r, c, cnt = self.window(hour_lo, hour_hi, True)
         return device.Counts(z, r, c, cnt, 0, [])
+
+    # -------------------------------------------------- viewports and tiles
+
+    def _view_args(self, rects, hours, group):
+        """Validated (int64 rectangle array, hour_lo, hour_hi, group word) of
+        hm_stream_view."""
+        rects = [tuple(int(v) for v in r) for r in rects]
+        if not 1 <= len(rects) <= _lib.HM_VIEW_MAX_RECTS or any(len(r) != 5 for r in rects):
+            raise ValueError("a view takes 1..%d rectangles (zoom, row_lo, row_hi, col_lo, col_hi)"
+                             % _lib.HM_VIEW_MAX_RECTS)
+        for z, rlo, rhi, clo, chi in rects:
+            if not self.zmin <= z <= self.zmax:
+                raise ValueError("rectangle zoom %d is outside the stream's %d..%d" % (z, self.zmin, self.zmax))
+            if rhi <= rlo or chi <= clo:
+                raise ValueError("empty rectangle %r (row_hi <= row_lo or col_hi <= col_lo)"
+                                 % ((z, rlo, rhi, clo, chi),))
+        if hours is None:
+            lo = hi = _lib.HM_STREAM_ALLTIME
+        else:
+            lo, hi = int(hours[0]), int(hours[1])
+            if hi <= lo:
+                raise ValueError("a window needs hour_lo < hour_hi (got %d, %d)" % (lo, hi))
+        if group == "merged":
+            gw = _lib.HM_VIEW_MERGED
+        elif group == "each":
+            gw = _lib.HM_VIEW_EACH
+        elif isinstance(group, (int, np.integer)) and 0 <= int(group) <= NOGROUP:
+            gw = int(group)
+        else:
+            raise ValueError("group must be 'merged', 'each' or a group id 0..0x%X (got %r)" % (NOGROUP, group))
+        return rects, lo, hi, gw
+
+    def view_device(self, rects, hours=None, group="merged"):
+        """(n, keys, counts, groups) as torch CUDA tensors: the cells inside
+        any of rects = [(zoom, row_lo, row_hi, col_lo, col_hi)] (lo inclusive,
+        hi exclusive, clipped to the square), of hours = None (every cell,
+        undated ones included) or (lo, hi), summed over every group
+        ('merged'), per group ('each') or of one group id (hm_stream_view;
+        out-of-square cells not included)."""
+        torch = self._torch
+        self.ctx.bind_stream()
+        rects, lo, hi, gw = self._view_args(rects, hours, group)
+        ra = (ctypes.c_int64 * (5 * len(rects)))(*[v for r in rects for v in r])
+        # merged and one-group views hold at most the rectangles' cells; an
+        # 'each' view starts from the last one of these rectangles (one
+        # HM_E_CAPACITY retry with the exact size when that is short)
+        area = sum((min(rhi, 1 << z) - max(rlo, 0)) * (min(chi, 1 << z) - max(clo, 0))
+                   for z, rlo, rhi, clo, chi in rects if min(rhi, chi) > 0 and max(rlo, clo) < (1 << z))
+        memo = self.__dict__.setdefault("_rollup_n", {})
+        mk = ("view", tuple(rects), gw if gw < 0 else 0)
+        if gw == _lib.HM_VIEW_EACH:
+            cap = max(1024, int(memo.get(mk, min(area, 1 << 20)) * 1.25) + 1024)
+        else:
+            cap = max(1024, min(area, int(memo.get(mk, 1 << 20) * 1.25) + 1024))
+        cap = min(max(1024, self._log_capacity()), cap)
+        dev = "cuda:%d" % self.device_index
+        while True:
+            keys = torch.empty(cap, dtype=torch.int64, device=dev)
+            counts = torch.empty(cap, dtype=torch.int64, device=dev)
+            groups = torch.empty(cap, dtype=torch.int32, device=dev)
+            n = ctypes.c_int64(0)
+            rc = self.ctx.L.hm_stream_view(self.ptr, lo, hi, gw, ra, len(rects), device._ptr(keys),
+                                           device._ptr(counts), device._ptr(groups), cap, ctypes.byref(n))
+            if rc == _lib.HM_E_CAPACITY and n.value > cap:
+                cap = n.value + 1024
+                continue
+            if rc != _lib.HM_OK:
+                _lib.raise_for(rc)
+            memo[mk] = n.value
+            return n.value, keys, counts, groups
+
+    def view(self, rects, hours=None, group="merged"):
+        """Host arrays (group u32, zoom, row, col, count) of the view, with
+        the out-of-square cells that lie in the rectangles as given (not
+        clipped)."""
+        n, keys, counts, groups = self.view_device(rects, hours, group)
+        z, r, c = device.decode_keys(keys[:n].cpu().numpy().view(np.uint64))
+        out = (groups[:n].cpu().numpy().view(np.uint32), z, r, c, counts[:n].cpu().numpy())
+        if not len(self._x):
+            return out
+        x = _view_records(self._x, [tuple(int(v) for v in q) for q in rects], hours, group)
+        return tuple(np.concatenate([a, x[:, j].astype(a.dtype)]) for j, a in enumerate(out))
+
+    def view_counts(self, rects, hours=None) -> device.Counts:
+        """Cells of every kept point inside the rectangles (and the hours)."""
+        _, z, r, c, cnt = self.view(rects, hours, "merged")
+        return device.Counts(z, r, c, cnt, 0, [])
+
+    def tile_cells(self, tiles, hours=None, label=None, user=None, max_zoom_level=None, delta=None) -> "_hm.Cells":
+        """The bins of the rows of the heatmap row tiles [(tz, tr, tc)]: those
+        of window_cells(lo, hi, label) for hours = (lo, hi), of
+        heatmap_cells('alltime') for hours = None, restricted to the tiles (and
+        to the rows of the group label `user`, when given).  Each tile is one
+        rectangle of a device view (tile_rects), 32 tiles per query."""
+        d = _hm.DETAIL_ZOOM_DELTA if delta is None else int(delta)
+        mz = self.zmax - d if max_zoom_level is None else int(max_zoom_level)
+        if mz + d != self.zmax or self.zmin > d + 1:
+            raise ValueError("rows need zooms %d..%d; the stream holds %d..%d" % (d + 1, mz + d, self.zmin, self.zmax))
+        if hours is None:
+            label = "alltime"
+        elif not isinstance(label, str) or _hm.KEY_SEPERATOR in label:
+            raise ValueError("window label %r must be a string without the key separator %r"
+                             % (label, _hm.KEY_SEPERATOR))
+        elif int(hours[1]) <= int(hours[0]):
+            raise ValueError("a window needs hour_lo < hour_hi (got %d, %d)" % (hours[0], hours[1]))
+        if self._explicit_max >= len(self.labels):
+            raise ValueError("rows need a label per group: group id %d was passed as group= and has none "
+                             "(feed the stream with user_id= to build rows)" % self._explicit_max)
+        tiles = sorted({tuple(int(v) for v in t) for t in tiles})
+        for tz, tr, tc in tiles:
+            if not 1 <= tz <= mz or not (0 <= tr < (1 << tz) and 0 <= tc < (1 << tz)):
+                raise ValueError("tile %r is not a heatmap row tile of zooms 1..%d inside the square"
+                                 % ((tz, tr, tc), mz))
+        gid = None if user is None else self._index.get(user, -1)
+        det = self._x[self._x[:, 2] == self.zmax]
+        if len(det) and not _hm._in_chain_window(det[:, 3], det[:, 4], self.zmax, d).all():
+            # side records outside the chain windows move between tiles (ChainFix):
+            # every cell is needed, the rows are filtered afterwards
+            cells = (self.heatmap_cells("alltime", max_zoom_level, delta) if hours is None else
+                     self.window_cells(hours[0], hours[1], label, max_zoom_level, delta))
+            want = set(tiles)
+            m = np.array([t in want for t in zip(*(a.tolist() for a in cells.row_tiles()))], dtype=bool)
+            return _cells_subset(cells, m if gid is None else m & (np.asarray(cells.label) == gid))
+        # one group's rows are its own cells: a group-select query (the literal
+        # 'all' rows, group 0, need every group's; an unknown label has none)
+        select = gid is not None and gid > 0
+        todo = range(0, len(tiles) if gid != -1 else 0, _lib.HM_VIEW_MAX_RECTS)
+        parts = [self.view(tile_rects(tiles[j:j + _lib.HM_VIEW_MAX_RECTS], d), hours, gid if select else "each")
+                 for j in todo]
+        gg, gz, gr, gc, gn = (np.concatenate([p[j] for p in parts]).astype(np.int64) if parts else
+                              np.zeros(0, np.int64) for j in range(5))
+        if select:
+            return _hm.Cells(self.labels, gg, gz, gr, gc, gn.astype(np.float64), d, [label])
+        # n: every group's cells summed; the grouped cells: those with a label
+        al = _sum_records(np.stack([gz, gr, gc, gn], axis=1), 3)
+        q = gg != NOGROUP
+        cells = _hm.combine_cells(self.labels, (al[:, 0], al[:, 1], al[:, 2], al[:, 3]),
+                                  (gg[q], gz[q], gr[q], gc[q], gn[q]), mz + d, d, label)
+        return cells if gid is None else _cells_subset(cells, np.asarray(cells.label) == gid)
+
+    def tile_rows(self, tiles, hours=None, label=None, user=None, max_zoom_level=None, delta=None) -> dict:
+        """{row_id: {bin_id: float}}: exactly the entries of window_rows(lo,
+        hi, label) (rows('alltime') for hours = None) whose tile is in tiles
+        = [(tz, tr, tc)], or those of the group label `user` alone; tiles
+        without data have no row."""
+        return _hm.cells_to_rows(self.tile_cells(tiles, hours, label, user, max_zoom_level, delta))
+
+    def tile_table(self, tiles, hours=None, label=None, user=None, max_zoom_level=None, delta=None):
+        """The same rows as a pyarrow Table(id, heatmap JSON)."""
+        return _hm.cells_to_table(self.tile_cells(tiles, hours, label, user, max_zoom_level, delta))
 
     def expire(self, before_hour: int):
         """Retention: drop the cells of every hour < before_hour (undated

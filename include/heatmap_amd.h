@@ -251,7 +251,29 @@ int hm_last_stats(hm_ctx* ctx, int64_t* slow_points, double* stage_us, int n_sta
  *                     window without data is HM_OK with *n_out = 0; hour_hi <=
  *                     hour_lo is HM_E_ARG.  groups_out may be NULL.  Keys and
  *                     HM_E_CAPACITY as hm_stream_rollup.
- *   hm_stream_expire  retention: drops every cell of a dated hour < before_hour
+ *   hm_stream_view    a viewport: the cells inside any of nrects rectangles
+ *                     (1 .. HM_VIEW_MAX_RECTS; rects: host int64[5 * nrects],
+ *                     zoom, row_lo, row_hi, col_lo, col_hi per rectangle: the
+ *                     cells of that zoom with row_lo <= row < row_hi and col_lo
+ *                     <= col < col_hi; a cell in several rectangles is returned
+ *                     once), of the dated hours hour_lo <= hour < hour_hi
+ *                     (clamped as a window's; undated cells are in none) or,
+ *                     with hour_lo == hour_hi == HM_STREAM_ALLTIME, of every
+ *                     cell, undated ones included; group = HM_VIEW_MERGED (one
+ *                     sum per cell, group 0xFFFFFFFF), HM_VIEW_EACH (one record
+ *                     per (group, cell)) or one group id 0 .. 0xFFFFFFFE
+ *                     (0xFFFFFFFE: the cells without a group).  One pass over
+ *                     the log's keys filters it; only the survivors are merged
+ *                     and emitted, so the cost beyond that pass follows the
+ *                     viewport, not the log.  Rectangle bounds are clipped to
+ *                     [0, 2^zoom]; one wholly outside the square selects
+ *                     nothing.  HM_E_ARG: nrects out of range, a zoom outside
+ *                     [zmin, zmax], row_hi <= row_lo, col_hi <= col_lo, hour_hi
+ *                     <= hour_lo other than the alltime pair, any other group
+ *                     value.  A view without cells is HM_OK with *n_out = 0.
+ *                     groups_out may be NULL.  Keys and HM_E_CAPACITY as
+ *                     hm_stream_rollup.  The log is left as it is.
+ *   hm_stream_expire retention: drops every cell of a dated hour < before_hour
  *                     (undated cells have no time and stay) in one pass over the
  *                     log, and moves the surviving (group, hour) buckets to a
  *                     fresh table: *cells_dropped cells left the log and
@@ -284,6 +306,11 @@ int hm_stream_extract(hm_stream* s, int64_t hour, uint64_t* keys_out, uint64_t* 
                       int64_t capacity, int64_t* n_out);
 int hm_stream_window(hm_stream* s, int64_t hour_lo, int64_t hour_hi, int merge_groups, uint64_t* keys_out,
                      uint64_t* counts_out, uint32_t* groups_out, int64_t capacity, int64_t* n_out);
+#define HM_VIEW_MAX_RECTS 32
+#define HM_VIEW_MERGED (-1)   /* summed over every group: group = 0xFFFFFFFF */
+#define HM_VIEW_EACH (-2)     /* per group */
+int hm_stream_view(hm_stream* s, int64_t hour_lo, int64_t hour_hi, int64_t group, const int64_t* rects, int nrects,
+                   uint64_t* keys_out, uint64_t* counts_out, uint32_t* groups_out, int64_t capacity, int64_t* n_out);
 int hm_stream_expire(hm_stream* s, int64_t before_hour, int64_t* cells_dropped, int64_t* buckets_freed);
 int hm_stream_destroy(hm_stream* s);
 

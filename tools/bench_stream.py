@@ -23,6 +23,19 @@ GB/s over 16 B per log cell read plus 16 B per survivor written, next to the
 library's read-stream kernel over the same bytes (hm_bench_read), and the
 log's cells, capacity and the bucket count after every batch: with retention
 they stop growing once H + 1 hours are resident.
+
+    python tools/bench_stream.py --retain 24 --batches 30 --warmup 0 --view --out profiles/stream_view.json
+
+--view: on the steady retained log, window(newest - H, newest + 1) against
+view (hm_stream_view) of the same hours for two viewports -- (a) one heatmap
+tile, the 32 x 32 block of detail zoom 13 around the heaviest zoom-13 cell, and
+(b) a 4 x 3-tile screen at each of the detail zooms 8, 13 and 18 (3
+rectangles) -- as host ms around the call, 15 repetitions each (interleaved),
+median and range, with the cells out and a check that the view's cells equal
+the window's filtered by rectangle on the host.  --window-only times the
+window alone (the script then needs nothing newer than hm_stream_window, so a
+checkout of an earlier commit can run it on the same log); --parent-json FILE
+puts that run's "window" into this one's result as "parent_window".
 """
 import argparse
 import json
@@ -76,6 +89,70 @@ def read_rate(s, nbytes, reps=5):
     return best
 
 
+VIEW_REPS = 15
+
+
+def _screen(key, tiles_rows, tiles_cols):
+    """(zoom, row_lo, row_hi, col_lo, col_hi) of tiles_rows x tiles_cols
+    heatmap tiles (32 x 32 cells each) around the tile of the cell `key`"""
+    z, r, c = key >> 58, (key >> 29) & 0x1FFFFFFF, key & 0x1FFFFFFF
+    tr, tc = (r >> 5) - (tiles_rows - 1) // 2, (c >> 5) - (tiles_cols - 1) // 2
+    return (z, tr << 5, (tr + tiles_rows) << 5, tc << 5, (tc + tiles_cols) << 5)
+
+
+def view_bench(s, a, lo, hi):
+    """--view (module docstring) on the stream as it stands"""
+    import numpy as np
+
+    n, keys, counts, _ = s.window_device(lo, hi)
+    k, cnt = keys[:n], counts[:n]
+    out = {"hours": [lo, hi], "reps": VIEW_REPS, "log_cells": s.cells()[0], "window_cells": n,
+           "timing": "host ms around the call (ends in a synchronise), window and views interleaved"}
+    t_win = []
+    if a.window_only:
+        for _ in range(VIEW_REPS):
+            t_win.append(_ms(lambda: s.window_device(lo, hi))[0])
+        out["window"] = _stats(t_win)
+        return out
+    heavy = {}
+    for z in (8, 13, 18):
+        m = (k >> 58) == z
+        heavy[z] = int(k[torch.argmax(torch.where(m, cnt, torch.full_like(cnt, -1)))].item())
+    ports = {"a_one_tile_z13": [_screen(heavy[13], 1, 1)],
+             "b_screen_4x3_z8_z13_z18": [_screen(heavy[z], 3, 4) for z in (8, 13, 18)]}
+    hk, hc = k.cpu().numpy(), cnt.cpu().numpy()
+    hz, hr, hcol = hk >> 58, (hk >> 29) & 0x1FFFFFFF, hk & 0x1FFFFFFF
+    t_view = {name: [] for name in ports}
+    for name, rects in ports.items():
+        s.view_device(rects, (lo, hi))          # warm: code object, the capacity memo
+    for _ in range(VIEW_REPS):
+        t_win.append(_ms(lambda: s.window_device(lo, hi))[0])
+        for name, rects in ports.items():
+            t_view[name].append(_ms(lambda: s.view_device(rects, (lo, hi)))[0])
+    out["window"] = _stats(t_win)
+    ok = True
+    for name, rects in ports.items():
+        nv, vk, vc, _ = s.view_device(rects, (lo, hi))
+        m = np.zeros(hk.size, dtype=bool)
+        for z, rlo, rhi, clo, chi in rects:
+            m |= (hz == z) & (hr >= rlo) & (hr < rhi) & (hcol >= clo) & (hcol < chi)
+        gk, gc = vk[:nv].cpu().numpy(), vc[:nv].cpu().numpy()
+        og, ow = np.argsort(gk), np.argsort(hk[m])
+        same = nv == int(m.sum()) and nv > 0 and np.array_equal(gk[og], hk[m][ow]) and \
+            np.array_equal(gc[og], hc[m][ow])
+        ok &= bool(same)
+        out[name] = {"rects": [list(map(int, q)) for q in rects], "cells_out": nv, "ms": _stats(t_view[name]),
+                     "equals_filtered_window": bool(same)}
+    out["check"] = "ok" if ok else "FAIL"
+    if a.parent_json:
+        pj = json.load(open(a.parent_json))
+        out["parent_window"] = pj["view"]["window"]
+        out["parent_window_note"] = ("this script with --window-only run by a checkout of the parent commit (its "
+                                     "library and package) on the same seeded log, in the same session")
+        assert pj["view"]["window_cells"] == n and pj["view"]["log_cells"] == out["log_cells"]
+    return out
+
+
 def retain(a):
     """--retain H: a stream under retention (module docstring)"""
     n, H = int(a.batch), a.retain
@@ -104,7 +181,8 @@ def retain(a):
                 t_exp.append(ms_exp)
                 gbps.append(16.0 * (2 * llen - dropped) / (ms_exp * 1e-3) / 1e9)
     steady = [x for x in series if x["batch"] > H]
-    print(json.dumps({
+    view = view_bench(s, a, BASE + total - 1 - H, BASE + total) if a.view else None
+    result = json.dumps({
         "metric": "stream under retention: expire(newest - H) and window(newest - H, newest + 1) per one-hour batch",
         "retain_hours": H, "batch_points": n, "batches": a.batches, "warmup": a.warmup, "zooms": [a.zmin, a.zmax],
         "kind": a.kind, "ms_add": _stats(t_add), "ms_expire": _stats(t_exp), "ms_window": _stats(t_win),
@@ -116,8 +194,13 @@ def retain(a):
                          "buckets": sorted({x["buckets"] for x in steady}),
                          "cells_min_max": [min(x["cells"] for x in steady), max(x["cells"] for x in steady)]}
         if steady else None,
+        "view": view,
         "series": series,
-        "data": "synthetic (heatmap_amd.synth, generated on device, resident in HBM)"}))
+        "data": "synthetic (heatmap_amd.synth, generated on device, resident in HBM)"})
+    print(result)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(result + "\n")
     s.close()
 
 
@@ -134,6 +217,12 @@ def main():
                     help="the resident log's first capacity (it doubles when full)")
     ap.add_argument("--retain", type=int, default=0, metavar="H",
                     help="retention mode: one-hour batches, expire(newest - H) and one window query after each")
+    ap.add_argument("--view", action="store_true",
+                    help="with --retain: window vs viewport queries on the steady log (module docstring)")
+    ap.add_argument("--window-only", action="store_true", help="with --view: time the window alone")
+    ap.add_argument("--parent-json", default=None, metavar="FILE",
+                    help="with --view: a --window-only result of the parent commit, kept as parent_window")
+    ap.add_argument("--out", default=None, metavar="FILE", help="with --retain: also write the JSON line to FILE")
     a = ap.parse_args()
     if a.retain > 0:
         return retain(a)
