@@ -458,9 +458,6 @@ extern "C" int hm_project(hm_ctx* ctx, const double* lat, const double* lon, int
 /* [zmin, Z] (hm_general.hip).  *total = records (all of them, even past the   */
 /* capacity).  Errors (tiles beyond the key's range) go to the error word.      */
 /* ------------------------------------------------------------------------ */
-#ifndef HM_CS_FUSE
-#define HM_CS_FUSE 1   /* packed grouped records: two zoom steps per cascade launch (k_cascade2) */
-#endif
 static int gen_count(hm_ctx* ctx, const int64_t* row, const int64_t* col, const uint32_t* group, const int64_t* index,
                      uint64_t n, int Z, int zmin, const HmGenEmit& e, uint64_t* total, const double* lat = nullptr,
                      const double* lon = nullptr, const uint8_t* keep = nullptr)
@@ -588,7 +585,7 @@ static int gen_count(hm_ctx* ctx, const int64_t* row, const int64_t* col, const 
     ca.hic = down[1];
     /* packed records: two zoom steps per launch where two levels of records
      * are left before the last (k_cascade2) */
-    const bool fuse = HM_CS_FUSE && e.width == 2 && !e.split;
+    const bool fuse = e.width == 2 && !e.split;
     int in = cur;                       /* key buffer of the launch's input */
     uint32_t* ecur = nullptr;           /* ENDs of the input cells (none: raw keys) */
     uint32_t* eb[2] = {e0, e1};
@@ -827,7 +824,7 @@ static int count_impl(hm_ctx* ctx, const double* lat, const double* lon, const i
             ENSURE(B_L1_HIST, HM_D1 * 4, hist);
             ENSURE(B_L1_SMASK, HM_D1, smask);
             uint4* l1slot = nullptr;   /* k_l1_fast's slot table (lat/lon input) */
-            if (HM_L1_SLOTTAB && !from_tiles) ENSURE(B_L1_SLOT, (size_t)FS * sizeof(uint4), l1slot);
+            if (!from_tiles) ENSURE(B_L1_SLOT, (size_t)FS * sizeof(uint4), l1slot);
             /* hot tiles are level-2 buckets: zoom zs[1], a dense sample
              * histogram of <= 4^11 tiles.  In the two-level plan (level 1 at
              * z1, the last at zb) they skip every partition after level 1; in

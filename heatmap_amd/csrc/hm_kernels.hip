@@ -169,20 +169,14 @@ __device__ __forceinline__ void hm_pin_all(uint32_t (&x)[N], uint32_t& y)
 }
 
 /* the point stream: 16 GB per 1e9 points read once, with the non-temporal
- * hint (HM_L1_NT) so it does not push level 1's partly written key lines out
- * of L2 (each region line fills over many tiles; evicted early, it is written
- * back several times) */
-#ifndef HM_L1_NT
-#define HM_L1_NT 1
-#endif
+ * hint so it does not push level 1's partly written key lines out of L2
+ * (each region line fills over many tiles; evicted early, it is written back
+ * several times) */
 typedef double hm_d2v __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ double2 hm_stream_load2(const double2* p)
 {
-    if (HM_L1_NT) {
-        const hm_d2v v = __builtin_nontemporal_load((const hm_d2v*)p);
-        return make_double2(v.x, v.y);
-    }
-    return *p;
+    const hm_d2v v = __builtin_nontemporal_load((const hm_d2v*)p);
+    return make_double2(v.x, v.y);
 }
 
 /* hot-tile lookup of zoom-zb tile (rs, cs) in the LDS table image: h when the
@@ -629,17 +623,8 @@ __global__ __launch_bounds__(HM_P1_THREADS, HM_P1_WAVES) void k_project_partitio
 static_assert(HM_L1_CW >= HM_L1_SLOTS + 64 && HM_L1_CW % 64 == 0, "count and delta words pair as read2st64");
 static_assert(HM_L1_SLOTS % HM_P1_THREADS == 0, "slots per thread");
 
-#ifndef HM_L1_FAST
-#define HM_L1_FAST 1                        /* 0: k_project_partition, 1: k_l1_fast */
-#endif
-#ifndef HM_L1_LATE_DEST
-#define HM_L1_LATE_DEST 1                   /* destinations resolved after the staging (see the staging) */
-#endif
 #ifndef HM_L1_WAVES
 #define HM_L1_WAVES 4                       /* k_l1_fast: waves per SIMD its registers allow (4: 2 blocks of 8 waves per CU) */
-#endif
-#ifndef HM_L1_COPY_BATCH
-#define HM_L1_COPY_BATCH 1                  /* copy-out: 16 entry reads, 16 delta reads, then the stores */
 #endif
 
 /* k_l1_fast's slot -> level-1 digit (hot slot h: digit HM_MAX_F1 + h; cold
@@ -655,7 +640,7 @@ __device__ __forceinline__ bool hm_l1_slot_live(uint32_t sl, uint32_t H, uint32_
     return sl < HM_MAX_HOT ? sl < H : (sl - HM_MAX_HOT) < F;
 }
 
-/* the slot table of one call (HM_L1_SLOTTAB, hm_pipeline.h): 8 x 1536 entries,
+/* the slot table of one call (hm_pipeline.h): 8 x 1536 entries,
  * what every one of k_l1_fast's blocks used to work out for itself from
  * rbase, rcap and smask with five dependent scattered loads per slot */
 __global__ __launch_bounds__(256) void k_l1_slots(HmPart1Args a, uint4* __restrict__ tab)
@@ -702,7 +687,6 @@ k_l1_fast(HmPart1Args a)
     double* const tab = (double*)ent;
     uint2* const hot2 = (uint2*)((char*)ent + 16384);
     const int tid = threadIdx.x;
-    const int F = 1 << a.dbits;
     const uint32_t H = a.hot_z >= 0 ? *a.hot_n : 0u;
     const int64_t base = (a.tile0 + (int64_t)blockIdx.x) * HM_T1;
     HM_STAMP_M(4, 0);
@@ -714,15 +698,11 @@ k_l1_fast(HmPart1Args a)
     const double ghalf2 = 0.5 - scale * 0x1p-49;       /* column */
     constexpr int PERD = HM_L1_SLOTS / HM_P1_THREADS;
     const int wd = a.dbits >> 1;
-    /* slot -> digit (hot slot h: digit HM_MAX_F1 + h; cold slot: unskewed) */
-    auto digit_of = [&](uint32_t sl) -> uint32_t { return hm_l1_slot_digit(sl, wd); };
-    /* HM_L1_SLOTTAB: no liveness test anywhere.  A point's slot is a dummy, a
-     * hot tile the table holds (h < H) or the cold slot of its own digit
-     * (< F: an accepted point has r, c < 2^Z), so a dead slot's count word
-     * stays 0: it reserves nothing, its zero capacity fits its zero count,
-     * and the stage offset and delta it writes to its own words are never
-     * read */
-    auto live = [&](uint32_t sl) { return HM_L1_SLOTTAB ? true : hm_l1_slot_live(sl, H, (uint32_t)F); };
+    /* no liveness test anywhere.  A point's slot is a dummy, a hot tile the
+     * table holds (h < H) or the cold slot of its own digit (< F: an accepted
+     * point has r, c < 2^Z), so a dead slot's count word stays 0: it reserves
+     * nothing, its zero capacity fits its zero count, and the stage offset
+     * and delta it writes to its own words are never read */
     /* keep bytes, then the tables, then the points (vmcnt retires in order) */
     uint32_t kp[HM_P1_PPT / 2];   /* KEEP: the keep bytes (a keep-less call compiles the test away) */
     if (KEEP) {
@@ -741,7 +721,6 @@ k_l1_fast(HmPart1Args a)
         const int i = q * HM_P1_THREADS + tid;
         tv[q] = i >= HM_YTAB_N ? __builtin_nan("") : c_ytab[i];
     }
-#if HM_L1_SLOTTAB
     /* the owned slots' (base, capacity, fill index): one coalesced 16-B load
      * each; no address depends on a load, so nothing waits before the point
      * loads are out */
@@ -751,24 +730,8 @@ k_l1_fast(HmPart1Args a)
 #pragma unroll
         for (int q = 0; q < PERD; q++) st[q] = row[q * HM_P1_THREADS + tid];
     }
-#else
-    uint32_t smk[PERD], rcap2[PERD][2], rbase2[PERD][2];
-#pragma unroll
-    for (int q = 0; q < PERD; q++) {
-        const uint32_t sl = q * HM_P1_THREADS + tid;
-        const uint32_t d = digit_of(sl);
-        const uint32_t s0 = hm_l1i(d, 0), s1 = hm_l1i(d, blockIdx.x & (HM_L1_SHARDS - 1));
-        const bool lv = live(sl);
-        smk[q] = lv ? a.smask[d] : 0u;
-        rcap2[q][0] = lv ? a.rcap[s0] : 0u;
-        rcap2[q][1] = lv ? a.rcap[s1] : 0u;
-        rbase2[q][0] = lv ? a.rbase[s0] : 0u;
-        rbase2[q][1] = lv ? a.rbase[s1] : 0u;
-    }
-#endif
     constexpr int HV = HM_HOT_SLOTS / 4 / HM_P1_THREADS;
     uint4 hv[HV];
-#if HM_L1_SLOTTAB
     /* no branch around the loads (the join of "loaded" and "zero" cost an
      * s_waitcnt vmcnt(0) ahead of the point loads): without hot tiles they
      * read the first 16 KB of rbase, HM_D1 * HM_L1_SHARDS words, unused */
@@ -779,10 +742,6 @@ k_l1_fast(HmPart1Args a)
         const uint4 v = hsrc[j * HM_P1_THREADS + tid];
         hv[j] = make_uint4(v.x, v.y, v.z, v.w);
     }
-#else
-#pragma unroll
-    for (int j = 0; j < HV; j++) hv[j] = H ? ((const uint4*)a.hot_hash)[j * HM_P1_THREADS + tid] : make_uint4(0u, 0u, 0u, 0u);
-#endif
     __builtin_amdgcn_sched_barrier(0);
     double2 la[HM_P1_PPT / 2], lo[HM_P1_PPT / 2];
     {
@@ -911,15 +870,9 @@ k_l1_fast(HmPart1Args a)
 #pragma unroll
     for (int q = 0; q < PERD; q++) {
         const uint32_t sl = q * HM_P1_THREADS + tid;
-        cnt[q] = live(sl) ? cw[sl] : 0u;
+        cnt[q] = cw[sl];
         gpos[q] = 0;
-#if HM_L1_SLOTTAB
         if (cnt[q]) gpos[q] = atomicAdd(&a.fill[st[q].z], cnt[q]);
-#else
-        const uint32_t d = digit_of(sl);
-        const uint32_t sh = smk[q] != 0 ? (blockIdx.x & (HM_L1_SHARDS - 1)) : 0u;
-        if (cnt[q]) gpos[q] = atomicAdd(&a.fill[hm_l1i(d, sh)], cnt[q]);
-#endif
     }
     /* stage offsets: cold slots (q >= QH) first, hot slots (q < QH) after
      * them, from one scan of (cold count | hot count << 16) */
@@ -948,17 +901,10 @@ k_l1_fast(HmPart1Args a)
 #pragma unroll
         for (int q = 0; q < PERD; q++) {
             const uint32_t sl = q * HM_P1_THREADS + tid;
-            if (live(sl)) {
-#if HM_L1_SLOTTAB
-                const uint32_t rc = st[q].y, rb = st[q].x;
-#else
-                const uint32_t rc = smk[q] != 0 ? rcap2[q][1] : rcap2[q][0];
-                const uint32_t rb = smk[q] != 0 ? rbase2[q][1] : rbase2[q][0];
-#endif
-                const bool fits = (uint64_t)gpos[q] + cnt[q] <= (uint64_t)rc;
-                over |= cnt[q] && !fits;
-                cw[HM_L1_CW + sl] = (fits ? rb + gpos[q] : 0xFFF00000u) - offq[q];
-            }
+            const uint32_t rc = st[q].y, rb = st[q].x;
+            const bool fits = (uint64_t)gpos[q] + cnt[q] <= (uint64_t)rc;
+            over |= cnt[q] && !fits;
+            cw[HM_L1_CW + sl] = (fits ? rb + gpos[q] : 0xFFF00000u) - offq[q];
         }
         if (over) {
             atomicOr(a.overflow, 1ull);
@@ -968,13 +914,12 @@ k_l1_fast(HmPart1Args a)
 #pragma unroll
     for (int q = 0; q < PERD; q++) {
         const uint32_t sl = q * HM_P1_THREADS + tid;
-        if (live(sl)) cw[sl] = offq[q];
+        cw[sl] = offq[q];
     }
-    if (!HM_L1_LATE_DEST) deltas();
     hm_lds_barrier();
     HM_STAMP_M(4, 4);
     /* staging, branch-free: a point that stages nothing writes its lane's pad
-     * entry.  HM_L1_LATE_DEST: the entry holds its slot, and the destination
+     * entry.  The entry holds its slot, and the destination
      * deltas are written after the staging, so the reservation atomics'
      * round trip overlaps it (the copy-out looks the delta up per key) */
     /* (the compiler reads each offset under its point's select, one LDS
@@ -984,14 +929,9 @@ k_l1_fast(HmPart1Args a)
     for (int k = 0; k < HM_P1_PPT; k++) {
         const uint32_t o = cw[slot[k]];   /* (dummies: in range, unused) */
         const uint32_t pos = slot[k] < HM_L1_SLOTS ? o + rank[k] : HM_T1 + (uint32_t)hm_lane();
-        if (HM_L1_LATE_DEST) {
-            ent[pos] = make_uint2(key[k], slot[k]);
-        } else {
-            const uint32_t dl = cw[HM_L1_CW + slot[k]];
-            ent[pos] = make_uint2(key[k], dl + pos);
-        }
+        ent[pos] = make_uint2(key[k], slot[k]);
     }
-    if (HM_L1_LATE_DEST) deltas();
+    deltas();
     hm_lds_barrier();
     HM_STAMP_M(4, 5);
     /* copy-out: a wave stores 64 consecutive staged keys -- cold keys in [0, C)
@@ -1011,34 +951,24 @@ k_l1_fast(HmPart1Args a)
     };
     uint2 e[HM_P1_PPT];
     uint32_t sov;   /* s_over (the overflow flag rides in the delta batch) */
-    if (HM_L1_COPY_BATCH && HM_L1_LATE_DEST) {
-        /* three batches: the 16 entries, their 16 deltas, then the stores,
-         * with one wait between them.  An entry past total is stale stage
-         * (table words): its delta index is clamped into cw, not branched
-         * around, and what it reads is never stored */
-        uint32_t dl[HM_P1_PPT];
+    /* three batches: the 16 entries, their 16 deltas, then the stores, with
+     * one wait between them.  An entry past total is stale stage (table
+     * words): its delta index is clamped into cw, not branched around, and
+     * what it reads is never stored */
+    uint32_t dl[HM_P1_PPT];
 #pragma unroll
-        for (int j = 0; j < HM_P1_PPT; j++) {
-            e[j] = ent[j * HM_P1_THREADS + tid];
-            dl[j] = e[j].y;
-        }
-        hm_pin_all(dl);   /* (the key comes with the slot: one 8-B read) */
-#pragma unroll
-        for (int j = 0; j < HM_P1_PPT; j++) dl[j] = cw[HM_L1_CW + min(dl[j], (uint32_t)(HM_L1_CW - 1))];
-        sov = s_over;
-        hm_pin_all(dl, sov);
-        sov = __builtin_amdgcn_readfirstlane(sov);   /* block-uniform: a scalar branch, as before */
-#pragma unroll
-        for (int j = 0; j < HM_P1_PPT; j++) e[j].y = dl[j] + (uint32_t)(j * HM_P1_THREADS + tid);
-    } else {
-#pragma unroll
-        for (int j = 0; j < HM_P1_PPT; j++) {
-            const uint32_t i = j * HM_P1_THREADS + tid;
-            e[j] = ent[i];   /* past total: unused */
-            if (HM_L1_LATE_DEST) e[j].y = i < total ? cw[HM_L1_CW + e[j].y] + i : 0u;
-        }
-        sov = s_over;
+    for (int j = 0; j < HM_P1_PPT; j++) {
+        e[j] = ent[j * HM_P1_THREADS + tid];
+        dl[j] = e[j].y;
     }
+    hm_pin_all(dl);   /* (the key comes with the slot: one 8-B read) */
+#pragma unroll
+    for (int j = 0; j < HM_P1_PPT; j++) dl[j] = cw[HM_L1_CW + min(dl[j], (uint32_t)(HM_L1_CW - 1))];
+    sov = s_over;
+    hm_pin_all(dl, sov);
+    sov = __builtin_amdgcn_readfirstlane(sov);   /* block-uniform: a scalar branch, as before */
+#pragma unroll
+    for (int j = 0; j < HM_P1_PPT; j++) e[j].y = dl[j] + (uint32_t)(j * HM_P1_THREADS + tid);
     const uint32_t wofs = (uint32_t)tid & ~63u;
     if (!sov) {
 #pragma unroll
@@ -1066,441 +996,6 @@ k_l1_fast(HmPart1Args a)
         }
     }
     HM_STAMP_M(4, 6);
-}
-
-/* ------------------------------------------------------------------------ */
-/* level 1, persistent, with compute and writer waves (round 6): k_l1_ws     */
-/* ------------------------------------------------------------------------ */
-/* k_l1_fast keeps a tile's point loads, its reservation atomics and its key
- * stores in the same waves.  On gfx9 vmcnt retires in issue order, so a load
- * of the next tile issued by such a wave is waited for by each later atomic
- * or store of that wave: a block's points are in flight only while it waits
- * to project them, and a CU's point stream stops whenever both of its blocks
- * count, reserve, stage or copy out.
- *
- * k_l1_ws: one persistent 1024-thread block per CU walking tiles b, b + G, ...
- * of HM_TW = 12288 points, with two wave roles:
- *   compute waves 0-11 (768 threads x 16 points): project tile t, then issue
- *       the loads of tile t + G at once -- the only VMEM operations these
- *       waves issue, so nothing they do later waits behind them -- count +
- *       rank in LDS, take part in the slot scan, stage;
- *   writer waves 12-15 (256 threads): every global atomic and store: the
- *       reservations of tile t (issued as soon as its counts are complete,
- *       waited for a phase later) and the copy-out of tile t, which runs while
- *       the compute waves project tile t + G.
- * A round has five block barriers: count | scan (2) | offsets | stage.  The
- * polynomial and hot-tile tables stay in LDS for the block's life.  The keys,
- * regions, reservations and deferred points are k_l1_fast's.  LDS: 98.8 KB
- * stage + 31.8 KB tables + 21 KB slot words (one block per CU). */
-#ifndef HM_L1_WS
-#define HM_L1_WS 0                  /* 1: whole units of tiles through k_l1_ws (measured slower) */
-#endif
-#ifndef HM_WS_PREFETCH_LATE
-#define HM_WS_PREFETCH_LATE 0       /* 1: the next tile's loads after the count (fewer live VGPRs) */
-#endif
-#ifndef HM_WS_PREFETCH_RING
-#define HM_WS_PREFETCH_RING 0       /* 1: each point pair's next-tile load as soon as the pair is projected */
-#endif
-#ifndef HM_WS_C
-#define HM_WS_C 768                 /* compute threads: 12 waves */
-#endif
-#define HM_WS_W (1024 - HM_WS_C)    /* writer threads: the rest of a 1024-thread block */
-#define HM_WS_THREADS (HM_WS_C + HM_WS_W)
-#define HM_TW (HM_WS_C * HM_P1_PPT) /* points per tile: 12288 at 12 compute waves */
-#define HM_WS_NJ ((HM_TW + HM_WS_W - 1) / HM_WS_W)   /* staged entries per writer thread */
-#define HM_WS_DLT 2048              /* delta words (slot index masked to 11 bits) */
-/* tiles per unit: whole units of k_l1_ws tiles end on a k_l1_fast tile boundary */
-#define HM_WS_UNIT (HM_TW % HM_T1 == 0 ? 1 : (2 * HM_TW) % HM_T1 == 0 ? 2 : 4)
-static_assert(HM_P1_PPT == 16 && (HM_WS_UNIT * HM_TW) % HM_T1 == 0, "k_l1_ws: whole units end on a k_l1_fast tile");
-static_assert(HM_WS_C % 64 == 0 && HM_WS_W >= 64, "whole waves of both roles");
-static_assert(HM_L1_SLOTS == HM_WS_THREADS + HM_MAX_HOT && HM_MAX_HOT <= HM_WS_THREADS,
-              "k_l1_ws scan: thread t owns slot t, and slot t + 1024 when t < HM_MAX_HOT");
-static_assert(HM_L1_SLOTS % HM_WS_W == 0, "writer slots per thread");
-static_assert(HM_L1_CW <= HM_WS_DLT, "slot indices fit the delta table");
-
-template <typename OutT, bool KEEP>
-__global__ __launch_bounds__(HM_WS_THREADS) void k_l1_ws(HmPart1Args a, uint32_t ntiles)
-{
-    /* staged (key, slot) + one pad entry per lane */
-    __shared__ __attribute__((aligned(16))) uint2 ent[HM_TW + 64];
-    constexpr int YROWS = HM_YTAB_ROWS + 1;   /* + the NaN poison row (k_l1_fast) */
-    constexpr int YN = YROWS * HM_YTAB_STRIDE;
-    __shared__ __attribute__((aligned(16))) double tab[YN];
-    __shared__ __attribute__((aligned(16))) uint2 hot2[HM_HOT_SLOTS / 2];
-    __shared__ uint32_t cnt[HM_L1_CW];    /* per slot: count + rank atomics (+ 64 dummies) */
-    __shared__ uint32_t off[HM_L1_CW];    /* per slot: stage offset */
-    __shared__ uint32_t dlt[HM_WS_DLT];   /* per slot: destination - stage offset (writer waves) */
-    __shared__ uint32_t scr[HM_WS_THREADS / 64 + 1];
-    __shared__ uint32_t s_over, s_sync;
-    const int tid = threadIdx.x;
-    const uint32_t wave = __builtin_amdgcn_readfirstlane((uint32_t)tid >> 6);
-    const int F = 1 << a.dbits;
-    const uint32_t H = a.hot_z >= 0 ? *a.hot_n : 0u;
-    const uint32_t G = gridDim.x;
-    const int wd = a.dbits >> 1;
-    auto digit_of = [&](uint32_t sl) -> uint32_t {
-        if (sl < HM_MAX_HOT) return HM_MAX_F1 + sl;
-        const uint32_t u = sl - HM_MAX_HOT, m = (1u << wd) - 1u;
-        return HM_SKEW_CUR ? ((u & ~m) | ((u - ((u >> wd) << 3)) & m)) : u;
-    };
-    auto live = [&](uint32_t sl) {
-        return sl < HM_MAX_HOT ? sl < H : (sl - HM_MAX_HOT) < (uint32_t)F;
-    };
-    /* the slot scan, by all 1024 threads (the same three barriers in both
-     * roles): thread t owns slot t and, t < HM_MAX_HOT, slot t + 1024; the
-     * cold slots get the stage's front, the hot ones follow (k_l1_fast) */
-    auto scan_slots = [&](uint32_t& Cc, uint32_t& total) {
-        constexpr int NW = HM_WS_THREADS / 64;
-        /* thread-derived LDS addresses recomputed here: hoisted out of the
-         * tile loop they would hold registers across it */
-        const uint32_t tt = hm_opaque((uint32_t)tid), ln = tt & 63u;
-        const uint32_t s1 = tt + HM_WS_THREADS;
-        const bool two = tt < HM_MAX_HOT;
-        const uint32_t c0 = live(tt) ? cnt[tt] : 0u;
-        const uint32_t c1 = (two && live(s1)) ? cnt[s1] : 0u;
-        const uint32_t v = two ? (c1 | (c0 << 16)) : c0;
-        const uint32_t inc = hm_wave_incl_scan(v);
-        if (ln == 63) scr[wave] = inc;
-        hm_lds_barrier();
-        if (wave == 0) {
-            const uint32_t s = ln < NW ? scr[ln] : 0u;
-            const uint32_t si = hm_wave_incl_scan(s);
-            if (ln < NW) scr[ln] = si - s;
-            if (ln == NW - 1) scr[NW] = si;
-        }
-        hm_lds_barrier();
-        const uint32_t pre = scr[wave] + inc - v, tot = scr[NW];
-        Cc = tot & 0xFFFFu;
-        total = Cc + (tot >> 16);
-        const uint32_t oc = pre & 0xFFFFu;
-        if (two) {
-            off[tt] = Cc + (pre >> 16);
-            off[s1] = oc;
-        } else {
-            off[tt] = oc;
-        }
-        hm_lds_barrier();
-    };
-    if (wave < HM_WS_C / 64) {
-        /* ---------------- compute waves ---------------- */
-        const uint32_t ct = (uint32_t)tid;
-        double2 la[HM_P1_PPT / 2], lo[HM_P1_PPT / 2];
-        uint32_t kp[HM_P1_PPT / 2];
-        /* point pair kk of tile t (lanes interleaved: coalesced 16-B loads) */
-        auto load_pair = [&](uint32_t t, int kk) {
-            const int64_t b = (int64_t)t * HM_TW;
-            const uint32_t o = hm_opaque(ct);
-            if (KEEP) kp[kk] = ((const uint16_t*)(a.keep + b))[kk * HM_WS_C + o];
-            la[kk] = hm_stream_load2((const double2*)(a.lat + b) + kk * HM_WS_C + o);
-            lo[kk] = hm_stream_load2((const double2*)(a.lon + b) + kk * HM_WS_C + o);
-        };
-        auto load_tile = [&](uint32_t t) {
-#pragma unroll
-            for (int k = 0; k < HM_P1_PPT / 2; k++) load_pair(t, k);
-        };
-        if (!KEEP) {
-#pragma unroll
-            for (int k = 0; k < HM_P1_PPT / 2; k++) kp[k] = 0x0101;
-        }
-        load_tile(blockIdx.x);
-        hm_lds_barrier();   /* the writer waves filled the tables and zeroed the counts */
-        const int hb = a.restbits >> 1;
-        const uint32_t lowm = (1u << hb) - 1u;
-        const uint32_t keym = (uint32_t)((1ull << (2 * hb)) - 1ull);
-        const uint32_t wm = (1u << wd) - 1u;
-        const int hs = a.hot_z >= 0 ? a.Z - a.hot_z : 0;
-#if defined(HM_STAMPS) && HM_STAMPS == 6
-        /* phase cycles per block, summed over its tiles (tools/stamps.py stamps6) */
-        unsigned long long sacc[6] = {0, 0, 0, 0, 0, 0}, sprev = __builtin_amdgcn_s_memtime();
-        auto stamp = [&](int i) {
-            const unsigned long long now = __builtin_amdgcn_s_memtime();
-            sacc[i] += now - sprev;
-            sprev = now;
-        };
-#else
-        auto stamp = [&](int) {};
-#endif
-        for (uint32_t t = blockIdx.x; t < ntiles; t += G) {
-            const int64_t base = (int64_t)t * HM_TW;
-            /* the projection's f64 constants, k_l1_fast's values bit for bit,
-             * built per tile from an opaque 52-bit exponent shift in SGPRs:
-             * every one is a power-of-two multiple of a compile-time double
-             * (2^Z scaling is exact), so no 64-bit literal is materialised
-             * and hoisted into registers that live across the tile loop */
-            uint64_t zb = (uint64_t)a.Z << 52;
-            asm volatile("" : "+s"(zb));
-            constexpr double C180 = 180.0 * HM_INV360;   /* 180 kz = RN(180 RN(1/360)) 2^Z */
-            const double nscale = hm_u2d(hm_d2u(-1.0) + zb), hscale = hm_u2d(hm_d2u(0.5) + zb);
-            const double kz = hm_u2d(hm_d2u(HM_INV360) + zb);
-            const double c180 = hm_u2d(hm_d2u(C180) + zb);
-            const double ghalf = 0.5 - hm_u2d(hm_d2u(HM_Y_EPS) + zb);
-            const double ghalf2 = 0.5 - hm_u2d(hm_d2u(0x1p-49) + zb);
-            const uint32_t lane = hm_opaque((uint32_t)tid) & 63u;
-            const uint32_t dummy = HM_L1_SLOTS + lane;
-            uint32_t slot[HM_P1_PPT], key[HM_P1_PPT];
-            uint32_t redo = 0;
-            /* the next tile (the last round reloads its own tile: straight-line
-             * loads, no conditional register set) */
-            const uint32_t tn = t + G < ntiles ? t + G : t;
-#pragma unroll
-            for (int k = 0; k < HM_P1_PPT; k++) {
-                /* k_l1_fast's projection, statement for statement */
-                const double pa = (k & 1) ? la[k >> 1].y : la[k >> 1].x;
-                const double po = (k & 1) ? lo[k >> 1].y : lo[k >> 1].x;
-                const double dd = 90.0 - fabs(pa);
-                const uint32_t dh = (uint32_t)(hm_d2u(dd) >> 32);
-                constexpr uint32_t I0 = (1023u + HM_YTAB_E0) << HM_YTAB_K;
-                const uint32_t ii = min((dh >> (20 - HM_YTAB_K)) - I0, (uint32_t)HM_YTAB_ROWS);
-                const double dlo = hm_u2d((uint64_t)(dh & ~((1u << (20 - HM_YTAB_K)) - 1u)) << 32);
-                const double tt = dd - dlo;
-                const double* cf = tab + ii * HM_YTAB_STRIDE;
-                double p = cf[5];
-                p = fma(p, tt, cf[4]);
-                p = fma(p, tt, cf[3]);
-                p = fma(p, tt, cf[2]);
-                p = fma(p, tt, cf[1]);
-                p = fma(p, tt, cf[0]);
-                const double R = fma(copysign(p, pa), nscale, hscale);
-                const double fr = __builtin_amdgcn_fract(R);
-                const double y = fma(po, kz, c180);
-                const double fc = __builtin_amdgcn_fract(y);
-                const bool ok = (int)(dd >= 90.0 - HM_LAT_SQ) & (int)(fabs(fr - 0.5) < ghalf) &
-                                (int)(fabs(po) < 180.0) & (int)(fabs(fc - 0.5) < ghalf2);
-                const uint32_t r = (uint32_t)(int32_t)R;
-                const uint32_t c = (uint32_t)(int32_t)y;
-                const bool kept = ((kp[k >> 1] >> (8 * (k & 1))) & 0xFFu) != 0;
-                redo |= (uint32_t)!ok << k;
-                const uint32_t rd = r >> hb, cd = c >> hb;
-                const uint32_t rdw = (rd << wd) + HM_MAX_HOT;
-                uint32_t sl = HM_SKEW_CUR ? (((cd + (rd << 3)) & wm) | rdw) : (cd | rdw);
-                if (H) sl = min(hm_hot_find(hot2, r >> hs, c >> hs), sl);
-                key[k] = ((r << hb) | (c & lowm)) & keym;
-                slot[k] = (ok & kept) ? sl : dummy;
-                asm volatile("" : "+v"(slot[k]), "+v"(key[k]));
-                /* ring: the pair's registers are free, its next-tile load goes
-                 * out now (the loads stay ~one tile ahead, issued evenly over
-                 * the projection instead of in one burst after it) */
-                if (HM_WS_PREFETCH_RING && !HM_WS_PREFETCH_LATE && (k & 1)) load_pair(tn, k >> 1);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            stamp(0);   /* wait for the points + projection */
-            /* deferred points (rare; their returning atomic waits for every
-             * load this wave has in flight, so they go before the prefetch) */
-            if (__builtin_amdgcn_ballot_w64(redo != 0)) {
-                /* scalar lane picks and an opaque thread index: nothing of this
-                 * rare block is hoisted into registers that live across the loop */
-                const uint32_t cto = hm_opaque(ct);
-                uint32_t ws = 0;
-#pragma unroll
-                for (int k = 0; k < HM_P1_PPT; k++) {
-                    const bool rd = (redo >> k) & 1u;
-                    const uint64_t m = __builtin_amdgcn_ballot_w64(rd);
-                    if (m) {
-                        const int l = __builtin_ctzll(m);
-                        uint64_t b = 0;
-                        if (hm_lane() == l) b = atomicAdd(a.redo_count, (unsigned long long)__popcll(m));
-                        b = ((uint64_t)__builtin_amdgcn_readlane((uint32_t)(b >> 32), l) << 32) |
-                            __builtin_amdgcn_readlane((uint32_t)b, l);
-                        const uint64_t q = b + hm_mbcnt(m);
-                        if (rd && q < a.redo_cap)
-                            a.redo_idx[q] = (uint32_t)(base + 2 * ((int64_t)(k >> 1) * HM_WS_C + cto) + (k & 1));
-                        ws += (uint32_t)__popcll(m);
-                    }
-                }
-                if (hm_lane() == 0) atomicAdd(a.slow_count, (unsigned long long)ws);
-            }
-            if (!HM_WS_PREFETCH_RING && !HM_WS_PREFETCH_LATE) load_tile(tn);
-            /* count + rank (k_l1_fast) */
-            uint32_t rank[HM_P1_PPT];
-            uint32_t merged = 0;
-#pragma unroll
-            for (int k = 0; k < HM_P1_PPT; k++) {
-                const uint32_t k0 = __builtin_amdgcn_readfirstlane(slot[k]);
-                const uint64_t m = __builtin_amdgcn_ballot_w64(slot[k] == k0);
-                const uint32_t pm = (uint32_t)__builtin_popcount((uint32_t)m) + (uint32_t)__builtin_popcount((uint32_t)(m >> 32));
-                uint32_t idx = slot[k], inc = 1u;
-                if (pm >= HM_L1_MERGE_MIN) {
-                    merged |= 1u << k;
-                    const bool in = (m >> lane) & 1ull;
-                    idx = (in && lane != 0) ? dummy : idx;
-                    inc = lane == 0 ? pm : inc;
-                }
-                rank[k] = atomicAdd(&cnt[idx], inc);
-            }
-            if (merged) {
-#pragma unroll
-                for (int k = 0; k < HM_P1_PPT; k++)
-                    if ((merged >> k) & 1u) {
-                        const uint32_t k0 = __builtin_amdgcn_readfirstlane(slot[k]);
-                        const uint64_t m = __builtin_amdgcn_ballot_w64(slot[k] == k0);
-                        const uint32_t r0 = __builtin_amdgcn_readfirstlane(rank[k]);
-                        if ((m >> lane) & 1ull) rank[k] = r0 + hm_mbcnt(m);
-                    }
-            }
-            /* slot (11 bits) and rank (< 2^14) share a register from here */
-            uint32_t sr[HM_P1_PPT];
-#pragma unroll
-            for (int k = 0; k < HM_P1_PPT; k++) sr[k] = slot[k] | (rank[k] << 11);
-            if (HM_WS_PREFETCH_LATE) load_tile(tn);
-            stamp(1);   /* redo, prefetch issue, count + rank */
-            hm_lds_barrier();   /* counts complete: the writer waves reserve */
-            stamp(2);
-            uint32_t Cc, total;
-            scan_slots(Cc, total);
-            stamp(3);
-            /* staging, branch-free: a point that stages nothing writes its
-             * lane's pad entry; the entry holds the point's slot (the writer
-             * waves look the destination delta up per key) */
-#pragma unroll
-            for (int k = 0; k < HM_P1_PPT; k++) {
-                const uint32_t s = sr[k] & 2047u;
-                const uint32_t o = off[s];
-                const uint32_t pos = s < HM_L1_SLOTS ? o + (sr[k] >> 11) : HM_TW + (uint32_t)lane;
-                ent[pos] = make_uint2(key[k], s);
-            }
-            stamp(4);
-            hm_lds_barrier();   /* staged: the writer waves copy out */
-            stamp(5);
-        }
-        /* the last prefetch is a reload of a tile already counted: drain it */
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#if defined(HM_STAMPS) && HM_STAMPS == 6
-        if (tid == 0 && blockIdx.x < HM_STAMP_BLOCKS) {
-            for (int i = 0; i < 6; i++) g_stamps[blockIdx.x * 12 + i] = sacc[i];
-            g_stamps[blockIdx.x * 12 + 11] = (ntiles - blockIdx.x + G - 1) / G;
-        }
-#endif
-    } else {
-        /* ---------------- writer waves ---------------- */
-        const uint32_t wt = (uint32_t)tid - HM_WS_C;
-        /* the tables (while the compute waves' first points are in flight) */
-        for (int i = (int)wt; i < YN; i += HM_WS_W) tab[i] = i >= HM_YTAB_N ? __builtin_nan("") : c_ytab[i];
-        if (H)
-            for (int j = (int)wt; j < HM_HOT_SLOTS / 4; j += HM_WS_W) ((uint4*)hot2)[j] = ((const uint4*)a.hot_hash)[j];
-        for (int i = (int)wt; i < HM_L1_CW; i += HM_WS_W) cnt[i] = 0;
-        if (wt == 0) {
-            s_over = 0;
-            s_sync = 0;
-        }
-        /* reservation slots q * 256 + wt: their region (shard of this block) */
-        constexpr int WQ = HM_L1_SLOTS / HM_WS_W;
-        uint32_t fi[WQ], rc[WQ], rb[WQ];
-#pragma unroll
-        for (int q = 0; q < WQ; q++) {
-            const uint32_t sl = q * HM_WS_W + wt;
-            const uint32_t d = digit_of(sl);
-            const bool lv = live(sl);
-            const uint32_t sh = (lv && a.smask[d] != 0) ? (blockIdx.x & (HM_L1_SHARDS - 1)) : 0u;
-            fi[q] = hm_l1i(d, sh);
-            rc[q] = lv ? a.rcap[fi[q]] : 0u;
-            rb[q] = lv ? a.rbase[fi[q]] : 0u;
-        }
-        hm_lds_barrier();
-        char* const outb = (char*)a.keys_out;
-        char* const houtb = (char*)a.keys_hot;
-        const int hb = a.restbits >> 1;
-        const int hs = a.hot_z >= 0 ? a.Z - a.hot_z : 0;
-        const uint32_t hm = (1u << hs) - 1u;
-        const bool hot32 = a.hot_bytes == 4;
-        auto put_cold = [&](uint2 e) { *(OutT*)(outb + (uint64_t)e.y * sizeof(OutT)) = (OutT)e.x; };
-        /* a hot key: (row offset, col offset) in the hot tile, from the cold
-         * key -- u16 for a last-level bucket tile, u32 for a mid-level one */
-        auto hot_key = [&](uint32_t x) { return (((x >> hb) & hm) << hs) | (x & hm); };
-        uint32_t pc[WQ], gp[WQ];
-#pragma unroll
-        for (int q = 0; q < WQ; q++) pc[q] = gp[q] = 0;
-        uint32_t pC = 0, ptot = 0, nsync = 0;
-#if defined(HM_STAMPS) && HM_STAMPS == 6
-        unsigned long long sacc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, sprev = __builtin_amdgcn_s_memtime();
-        auto stamp = [&](int i) {
-            const unsigned long long now = __builtin_amdgcn_s_memtime();
-            sacc[i] += now - sprev;
-            sprev = now;
-        };
-#else
-        auto stamp = [&](int) {};
-#endif
-        /* the previous tile: destination deltas once its reservations are
-         * back, a writer-only rendezvous, then its keys leave lane-parallel */
-        auto copy_out = [&]() {
-            bool over = false;
-#pragma unroll
-            for (int q = 0; q < WQ; q++) {
-                const uint32_t sl = q * HM_WS_W + wt;
-                if (live(sl)) {
-                    const bool fits = (uint64_t)gp[q] + pc[q] <= (uint64_t)rc[q];
-                    over |= pc[q] && !fits;
-                    dlt[sl] = (fits ? rb[q] + gp[q] : 0xFFF00000u) - off[sl];
-                }
-            }
-            if (over) {
-                atomicOr(a.overflow, 1ull);
-                atomicOr(&s_over, 1u);
-            }
-            stamp(0);   /* deltas (the reservations waited for) */
-            nsync += HM_WS_W / 64;
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-            if (hm_lane() == 0) atomicAdd(&s_sync, 1u);
-            while (__atomic_load_n(&s_sync, __ATOMIC_RELAXED) < nsync) __builtin_amdgcn_s_sleep(1);
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-            const bool ov = __atomic_load_n(&s_over, __ATOMIC_RELAXED) != 0;   /* block-uniform */
-            stamp(1);   /* writer rendezvous */
-            /* the cold keys [0, pC) then the hot ones [pC, ptot), each range
-             * lane-consecutive (a wave stores 64 consecutive staged keys), no
-             * per-key kind test; a region that overflowed: destinations
-             * >= 0xFFF00000, dropped (the host re-runs the level) */
-            constexpr int JB = HM_WS_NJ < 16 ? HM_WS_NJ : 16;
-            auto range = [&](uint32_t lo, uint32_t hi, auto put) {
-#pragma unroll 1
-                for (uint32_t b0 = lo; b0 < hi; b0 += JB * HM_WS_W) {   /* block-uniform */
-                    uint2 e[JB];
-#pragma unroll
-                    for (int j = 0; j < JB; j++) {
-                        const uint32_t i = b0 + j * HM_WS_W + wt;
-                        e[j] = ent[min(i, (uint32_t)HM_TW)];
-                        e[j].y = dlt[e[j].y & (HM_WS_DLT - 1)] + i;   /* past hi: unused */
-                    }
-#pragma unroll
-                    for (int j = 0; j < JB; j++) {
-                        const uint32_t i = b0 + j * HM_WS_W + wt;
-                        if (i < hi && (!ov || e[j].y < 0xFFF00000u)) put(e[j]);
-                    }
-                }
-            };
-            range(0, pC, put_cold);
-            if (hot32)
-                range(pC, ptot, [&](uint2 e) { *(uint32_t*)(houtb + (uint64_t)e.y * 4u) = hot_key(e.x); });
-            else
-                range(pC, ptot, [&](uint2 e) { *(uint16_t*)(houtb + (uint64_t)e.y * 2u) = (uint16_t)hot_key(e.x); });
-            stamp(2);   /* copy-out */
-        };
-        bool have = false;
-        for (uint32_t t = blockIdx.x; t < ntiles; t += G) {
-            if (have) copy_out();
-            hm_lds_barrier();   /* this tile's counts are complete */
-            stamp(3);
-            if (wt == 0) s_over = 0;   /* every writer read it in copy_out */
-#pragma unroll
-            for (int q = 0; q < WQ; q++) {
-                const uint32_t sl = q * HM_WS_W + wt;
-                pc[q] = live(sl) ? cnt[sl] : 0u;
-                gp[q] = 0;
-                if (pc[q]) gp[q] = atomicAdd(&a.fill[fi[q]], pc[q]);   /* waited for in the next copy_out */
-            }
-            stamp(4);   /* reservations issued */
-            scan_slots(pC, ptot);
-            stamp(5);
-            for (int i = (int)wt; i < HM_L1_CW; i += HM_WS_W) cnt[i] = 0;   /* the scan has read them */
-            hm_lds_barrier();   /* staged */
-            stamp(6);
-            have = true;
-        }
-        if (have) copy_out();
-#if defined(HM_STAMPS) && HM_STAMPS == 6
-        if (wt == 0 && blockIdx.x < 4096)
-            for (int i = 0; i < 8; i++) g_stamps[(4096 + blockIdx.x) * 12 + i] = sacc[i];
-#endif
-    }
 }
 
 /* Sampled digit histogram of level 1 (every stride-th point, fast projection
@@ -3283,9 +2778,6 @@ __device__ uint64_t hm_bucket_pyramid(uint32_t* v, int lg, int z_top, uint64_t p
 #endif
 #define HM_AG_ROW(lg) ((1u << (lg)) + HM_AG_PADW)
 #define HM_AG_PADDED (128u * (128u + HM_AG_PADW))
-#ifndef HM_AG_STAGE
-#define HM_AG_STAGE 1   /* hm_reg_pyramid7: cells staged in the dead histogram, written a whole line per store */
-#endif
 static_assert(HM_AG_LG == 7 && HM_AG_CELLS == 128 * 128, "padded histogram");
 
 /* The lg = 7 bucket pyramid from registers (k_aggregate's single-item
@@ -3378,10 +2870,9 @@ __device__ __forceinline__ uint64_t hm_reg_pyramid7(uint32_t* grid, int z_top, u
     }
     __syncthreads();
     uint64_t base = *sbase + scr[w];
-#if HM_AG_STAGE
     /* the wave's cells staged in its share of the (now dead) histogram as
      * (level << 14 | cell, count) pairs and written out a whole line per
-     * store (HM_AG_STAGE; as k_small_pairs' hm_sp_flush) */
+     * store (as k_small_pairs' hm_sp_flush) */
     constexpr uint32_t SC = HM_AG_PADDED / NW / 2 / 64 * 64;   /* cells per wave */
     uint2* stg = (uint2*)grid + (uint32_t)w * SC;
     uint32_t fill = 0;
@@ -3411,18 +2902,6 @@ __device__ __forceinline__ uint64_t hm_reg_pyramid7(uint32_t* grid, int z_top, u
         if (nz) stg[fill + hm_mbcnt(m)] = make_uint2(((uint32_t)(z_top - z) << 14) | i, v);
         fill += (uint32_t)__builtin_popcountll(m);
     };
-#else
-    auto put = [&](bool nz, int z, int lg, uint32_t i, uint32_t v) {
-        const uint64_t m = __builtin_amdgcn_ballot_w64(nz);
-        const uint64_t pos = base + hm_mbcnt(m);
-        if (nz && pos < o.capacity) {
-            o.keys[pos] = hm_cell_key(z, prefix, lg, i);
-            o.counts[pos] = v;
-        }
-        base += (uint32_t)__builtin_popcountll(m);
-    };
-    const auto flush = [&]() {};
-#endif
     if (i0)
 #pragma unroll
         for (int j = 0; j < 16; j++)
@@ -3466,10 +2945,7 @@ __global__ __launch_bounds__(HM_AG_THREADS, 8) void k_aggregate(HmAggArgs a)
         __device__ __forceinline__ uint32_t sl(uint32_t k) { return k + (k >> lg) * HM_AG_PADW; }   /* padded row */
         __device__ __forceinline__ void cnt(uint32_t k, bool v)
         {
-            if (HM_AG_FAST)
-                hm_lds_count_fast(grid, dummy + (uint32_t)hm_lane(), sl(k), v);
-            else
-                hm_lds_count(grid, dummy, sl(k), v);
+            hm_lds_count_fast(grid, dummy + (uint32_t)hm_lane(), sl(k), v);
         }
         __device__ __forceinline__ void key(uint32_t k, bool v, uint32_t) { cnt(k, v); }
         __device__ __forceinline__ void add(uint32_t k, bool v) { atomicAdd(&grid[v ? sl(k) : dummy + (uint32_t)hm_lane()], 1u); }
@@ -3483,8 +2959,7 @@ __global__ __launch_bounds__(HM_AG_THREADS, 8) void k_aggregate(HmAggArgs a)
         {
             const uint32_t k0 = x.x & 0xFFFFu;
             const uint64_t m = __builtin_amdgcn_ballot_w64(v && k0 == __builtin_amdgcn_readfirstlane(k0));
-            if (!HM_AG_FAST || (uint32_t)__builtin_popcount((uint32_t)m) + (uint32_t)__builtin_popcount((uint32_t)(m >> 32)) >
-                                   HM_MERGE_MIN) {
+            if ((uint32_t)__builtin_popcount((uint32_t)m) + (uint32_t)__builtin_popcount((uint32_t)(m >> 32)) > HM_MERGE_MIN) {
                 cnt(x.x & 0xFFFFu, v);
                 cnt(x.x >> 16, v);
                 cnt(x.y & 0xFFFFu, v);
@@ -3919,11 +3394,11 @@ struct HmSmallMap {
     static __device__ __forceinline__ bool lane_in(uint32_t lane, uint32_t spb) { return LO ? true : lane < spb; }
 };
 
-/* the small buckets k_small_pairs takes (HM_SP_FUSED): <= 32 keys in <= 32
- * runs (two a wave pass) or 33-64 keys in <= 64 runs (one) */
+/* the small buckets k_small_pairs takes: <= 32 keys in <= 32 runs (two a
+ * wave pass) or 33-64 keys in <= 64 runs (one) */
 __device__ __forceinline__ bool hm_sp_fused_ok(uint32_t nk, uint32_t nr)
 {
-    return HM_SP_FUSED && nk <= 64 && nr <= (nk <= 32 ? 32u : 64u);
+    return nk <= 64 && nr <= (nk <= 32 ? 32u : 64u);
 }
 
 /* Persistent: a bucket is this instantiation's when LO < nkeys <= HI (larger
@@ -3948,58 +3423,11 @@ __global__ __launch_bounds__(HM_SPW_THREADS) void k_small_sort(HmAggArgs a)
         const bool small = in & (LO == 0 || nkl > LO) & (nkl <= HI);
         const uint32_t rbl = small ? a.B.rbase[bl] : 0u, nrl = small ? a.B.nruns[bl] : 0u;
         const uint32_t kbl = small ? a.B.keybase[bl] : 0u;
-        /* (HM_SP_FUSED: the <= 32-key, <= 4-run buckets are k_small_pairs') */
+        /* (the buckets hm_sp_fused_ok takes are k_small_pairs') */
         const bool pairb = LO == 0 && small && hm_sp_fused_ok(nkl, nrl);
         if (LO == 0 && in && (!small || pairb)) a.spcnt[bl] = 0;
         if (small && !pairb) a.totals[bl] = nkl;
         uint64_t m = __ballot(small && !pairb);
-        if constexpr (LO == 0 && !HM_SP_FUSED) {
-            /* buckets of <= 32 keys in <= 4 runs: two per pass of the wave */
-            uint64_t mt = __ballot(small && nkl <= 32 && nrl <= 4);
-            m &= ~mt;
-            const uint32_t j = lane & 31;
-            while (mt) {
-                const int sl = hm_pair_lane(mt);
-                const bool seg = sl >= 0;
-                const int sr = seg ? sl : 0;
-                /* (every shuffle with the whole wave active: a bpermute reads
-                 * garbage from a lane outside the exec mask) */
-                const uint32_t nk0 = __shfl(nkl, sr, 64);
-                const uint32_t b = __shfl(bl, sr, 64), nk = seg ? nk0 : 0u;
-                const uint32_t r0 = __shfl(rbl, sr, 64), nr = __shfl(nrl, sr, 64), kb = __shfl(kbl, sr, 64);
-                /* this lane's key: its run among the bucket's <= 4 */
-                uint32_t src = 0, acc = 0;
-                bool found = false;
-#pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    const uint2 run = (seg && (uint32_t)q < nr) ? a.in.run[r0 + q] : make_uint2(0, 0);
-                    if (!found && j < acc + run.y) {
-                        src = run.x + (j - acc);
-                        found = true;
-                    }
-                    acc += run.y;
-                }
-                const bool v_ok = seg && j < nk;
-                uint32_t v = 0xFFFFFFFFu;
-                if (v_ok) {
-                    const uint32_t key = (uint32_t)a.keys[src];
-                    const uint32_t cm = (1u << a.lg) - 1;
-                    v = hm_spread7(key & cm) | (hm_spread7(key >> a.lg) << 1);
-                }
-                hm_seg32_size<2>(v, lane);
-                if (v_ok) a.codes[kb + j] = (uint16_t)v;
-                const uint32_t nx = __shfl_down(v, 1, 64);
-                /* cells ended by this element (as in hm_small_sort), summed
-                 * over the 32-lane segment */
-                const uint32_t hl = (33u - (uint32_t)__clz((int)(v ^ nx))) >> 1;
-                uint32_t total = !v_ok ? 0u
-                                       : (j + 1 == nk) ? (uint32_t)__popc(zmask)
-                                                       : (uint32_t)__popc(zmask & ((1u << hl) - 1u));
-#pragma unroll
-                for (int o = 16; o > 0; o >>= 1) total += __shfl_xor(total, o, 64);
-                if (seg && j == 0) a.spcnt[b] = total;
-            }
-        }
         while (m) {
             const int i = __builtin_ctzll(m);
             m &= m - 1;
@@ -4050,7 +3478,7 @@ __global__ __launch_bounds__(HM_SPW_THREADS) void k_small_sort(HmAggArgs a)
     }
 }
 
-/* k_small_pairs (HM_SP_FUSED, round 6): the small buckets of <= 64 keys --
+/* k_small_pairs (round 6): the small buckets of <= 64 keys --
  * the skew cloud's background, ~24 keys per zoom-11 bucket, 4M of them --
  * gathered, sorted, counted AND emitted in one pass.  A wave pass ("row")
  * takes two buckets of <= 32 keys in <= 32 runs (one 32-lane segment each) or
@@ -4133,44 +3561,11 @@ __device__ __forceinline__ uint32_t hm_sp_sort(const HmAggArgs& a, uint32_t key,
     return total;
 }
 
-/* the cells of one sorted row segment at q: a cell is written by its last
- * element, its count = that position - the segment's last head at or below */
-template <int W>
-__device__ __forceinline__ void hm_sp_emit(const HmAggArgs& a, uint32_t v, bool v_ok, uint32_t nk, uint64_t coord,
-                                           uint64_t q, uint32_t zmask, uint32_t lane)
-{
-    const uint32_t j = lane & (W - 1);
-    const uint64_t segm = W == 64 ? ~0ull : (lane >> 5) ? 0xFFFFFFFF00000000ull : 0x00000000FFFFFFFFull;
-    const uint32_t nx = __shfl_down(v, 1, 64), pv = __shfl_up(v, 1, 64);
-    /* the element's row and column offsets in the bucket, de-interleaved
-     * once: a level-l cell's are these >> l (hm_cell_key's layout) */
-    const uint32_t cr = hm_compact7(v >> 1), cc = hm_compact7(v);
-    const uint32_t crow = (uint32_t)(coord >> 32), ccol = (uint32_t)coord;
-    for (int l = 0; l < a.lg; l++) {
-        if (!((zmask >> l) & 1u)) continue;
-        const bool head = v_ok && ((j == 0) | ((pv >> (2 * l)) != (v >> (2 * l))));
-        const bool end = v_ok && ((j + 1 == nk) | ((nx >> (2 * l)) != (v >> (2 * l))));
-        /* the cell's first element: the last head at or below this lane (the
-         * segment's element 0 is one), as a position in the segment */
-        const uint64_t hm = __ballot(head) & ((2ull << lane) - 1ull);
-        const uint32_t start = (hm ? 63u - (uint32_t)__clzll((long long)hm) : 0u) & (uint32_t)(W - 1);
-        const uint64_t bal = __ballot(end) & segm;
-        if (end) {
-            const int s = a.lg - l;
-            const uint32_t row = (crow << s) | (cr >> l), col = (ccol << s) | (cc >> l);
-            const uint64_t pos = q + hm_mbcnt(bal);
-            if (pos < a.out.capacity) {
-                a.out.keys[pos] = ((uint64_t)(a.Z - l) << 58) | ((uint64_t)row << 29) | col;
-                a.out.counts[pos] = (uint64_t)(j - start + 1);
-            }
-        }
-        q += (uint64_t)__popcll(bal);
-    }
-}
-
-/* HM_SPP_STAGE: the same cells staged in the wave's LDS buffer as one u32
- * each -- bucket lane (6 bits) | level (3) | row (7) | column (7) | count (7)
- * -- at q (per lane, relative to the buffer), for hm_sp_flush to write out */
+/* the cells of one sorted row segment (a cell is written by its last element,
+ * its count = that position - the segment's last end below it) staged in the
+ * wave's LDS buffer as one u32 each -- bucket lane (6 bits) | level (3) |
+ * row (7) | column (7) | count (7) -- at q (per lane, relative to the buffer),
+ * for hm_sp_flush to write out */
 template <int W>
 __device__ __forceinline__ void hm_sp_stage(const HmAggArgs& a, uint32_t v, bool v_ok, uint32_t nk, uint32_t b,
                                             uint32_t q, uint32_t zmask, uint32_t lane, uint32_t* sb)
@@ -4201,7 +3596,7 @@ __device__ __forceinline__ void hm_sp_stage(const HmAggArgs& a, uint32_t v, bool
 
 /* n staged cells to keys / counts [g, g + n): every lane two 8-B stores of
  * consecutive cells, so each 64-B line is written whole by one instruction
- * (the per-level stores of hm_sp_emit leave lines written in pieces by
+ * (a store per cell and level as it ends leaves lines written in pieces by
  * several instructions; skew aggregation 3.88-3.92 -> 3.53-3.77 ms,
  * profiles/r6/small_pairs_block_res_ab.jsonl) */
 __device__ __forceinline__ void hm_sp_flush(const HmAggArgs& a, const uint32_t* sb, uint32_t n, uint64_t g,
@@ -4240,9 +3635,7 @@ __global__ __launch_bounds__(64 * NWB) void k_small_pairs(HmAggArgs a)
 {
     __shared__ uint16_t cds[NWB][HM_SPP_ROWS][64];   /* a round's rows of sorted codes per wave */
     __shared__ uint2 gsc[NWB][64];          /* hm_sp_key's run marks */
-#if HM_SPP_STAGE
     __shared__ uint32_t sbuf[NWB][HM_SPP_STAGE_CELLS];   /* staged cells (hm_sp_stage) */
-#endif
     __shared__ uint32_t s_wtot[NWB];        /* the round's cells per wave */
     __shared__ unsigned long long s_base;   /* the round's reservation */
     __shared__ uint32_t s_batch;            /* the block's next batch */
@@ -4375,7 +3768,6 @@ __global__ __launch_bounds__(64 * NWB) void k_small_pairs(HmAggArgs a)
             const uint64_t base = s_base + wpre;
             /* pass 2: the same rows in the same order, codes from LDS */
             uint64_t mp2 = mp, ms2 = ms;
-#if HM_SPP_STAGE
             /* the cells go through the wave's LDS buffer (rows in order: the
              * wave's cells are written in order), flushed before a row that
              * does not fit and at the end */
@@ -4386,10 +3778,8 @@ __global__ __launch_bounds__(64 * NWB) void k_small_pairs(HmAggArgs a)
                 __builtin_amdgcn_wave_barrier();
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
             };
-#endif
             for (uint32_t p = 0; p < ((mp | ms) ? nrows : 0u); p++) {
                 const uint32_t v = cds[wc][p][lane];
-#if HM_SPP_STAGE
                 const uint32_t rlo = __shfl(excl, (int)(2 * p), 64), rhi = __shfl(incl, (int)(2 * p + 1), 64);
                 if (rhi - flushed > HM_SPP_STAGE_CELLS) {
                     sync_sb();
@@ -4397,44 +3787,29 @@ __global__ __launch_bounds__(64 * NWB) void k_small_pairs(HmAggArgs a)
                     sync_sb();
                     flushed = rlo;
                 }
-#endif
                 if (mp2) {
                     const int sl = hm_pair_lane(mp2);
                     const bool seg = sl >= 0;
                     const int sr = seg ? sl : 0;
                     const uint32_t nk0 = __shfl(nkl, sr, 64);
                     const uint32_t nk = seg ? nk0 : 0u;
-#if HM_SPP_STAGE
                     const uint32_t q = __shfl(excl, (int)(2 * p + (lane >> 5)), 64) - flushed;
                     hm_sp_stage<32>(a, v == 0xFFFFu ? 0xFFFFFFFFu : v, seg && (lane & 31u) < nk, nk, (uint32_t)sr, q, zmask,
                                     lane, sb);
-#else
-                    const uint64_t coord = __shfl(cl, sr, 64);
-                    const uint64_t q = base + __shfl(excl, (int)(2 * p + (lane >> 5)), 64);
-                    hm_sp_emit<32>(a, v == 0xFFFFu ? 0xFFFFFFFFu : v, seg && (lane & 31u) < nk, nk, coord, q, zmask, lane);
-#endif
                 } else {
                     const int i = __builtin_ctzll(ms2);
                     ms2 &= ms2 - 1;
                     const uint32_t nk = __shfl(nkl, i, 64);
-#if HM_SPP_STAGE
                     const uint32_t q = __shfl(excl, (int)(2 * p), 64) - flushed;
                     hm_sp_stage<64>(a, v == 0xFFFFu ? 0xFFFFFFFFu : v, lane < nk, nk, (uint32_t)i, q, zmask, lane, sb);
-#else
-                    const uint64_t coord = __shfl(cl, i, 64);
-                    const uint64_t q = base + __shfl(excl, (int)(2 * p), 64);
-                    hm_sp_emit<64>(a, v == 0xFFFFu ? 0xFFFFFFFFu : v, lane < nk, nk, coord, q, zmask, lane);
-#endif
                 }
             }
-#if HM_SPP_STAGE
             {
                 const uint32_t wt = __builtin_amdgcn_readlane(incl, 63);
                 sync_sb();
                 hm_sp_flush(a, sb, wt - flushed, base + flushed, cl, lane);
                 sync_sb();
             }
-#endif
             mp = mp1;
             ms = ms1;
             rr ^= 1u;
@@ -4489,51 +3864,9 @@ __global__ __launch_bounds__(HM_SPW_THREADS) void k_small_emit(HmAggArgs a)
         const uint64_t cl = small ? a.B.coord[bl] : 0ull;
         const uint64_t ol = small ? a.spoff[bl] : 0ull;
         uint64_t m = __ballot(small);
-        if constexpr (LO == 0 && HM_SP_FUSED) {
+        if constexpr (LO == 0) {
             const uint32_t nrl = small ? a.B.nruns[bl] : 0u;
             m &= ~__ballot(small && hm_sp_fused_ok(nkl, nrl));   /* k_small_pairs' */
-        }
-        if constexpr (LO == 0 && !HM_SP_FUSED) {
-            /* the <= 32-key buckets in pairs, as k_small_sort took them */
-            const uint32_t nrl = small ? a.B.nruns[bl] : 0u;
-            uint64_t mt = __ballot(small && nkl <= 32 && nrl <= 4);
-            m &= ~mt;
-            const uint32_t j = lane & 31;
-            const uint64_t segm = (lane >> 5) ? 0xFFFFFFFF00000000ull : 0x00000000FFFFFFFFull;
-            while (mt) {
-                const int sl = hm_pair_lane(mt);
-                const bool seg = sl >= 0;
-                const int sr = seg ? sl : 0;
-                const uint32_t nk0 = __shfl(nkl, sr, 64);   /* whole wave active (see k_small_sort) */
-                const uint32_t nk = seg ? nk0 : 0u, kb = __shfl(kbl, sr, 64);
-                const uint64_t coord = __shfl(cl, sr, 64);
-                uint64_t q = base + __shfl(ol, sr, 64);
-                const bool v_ok = seg && j < nk;
-                const uint32_t v = v_ok ? (uint32_t)a.codes[kb + j] : 0xFFFFFFFFu;
-                const uint32_t nx = __shfl_down(v, 1, 64), pv = __shfl_up(v, 1, 64);
-                for (int l = 0; l < a.lg; l++) {
-                    if (!((zmask >> l) & 1u)) continue;
-                    const bool head = v_ok && ((j == 0) | ((pv >> (2 * l)) != (v >> (2 * l))));
-                    const bool end = v_ok && ((j + 1 == nk) | ((nx >> (2 * l)) != (v >> (2 * l))));
-                    /* the segment's last head at or below this lane (its j = 0
-                     * lane is one): the cell's first element */
-                    const uint64_t hm = __ballot(head) & ((2ull << lane) - 1ull);
-                    const uint32_t hl = hm ? 63u - (uint32_t)__clzll((long long)hm) : 0u;
-                    const uint32_t start = (uint32_t)__shfl((int)j, (int)hl, 64);
-                    const uint64_t bal = __ballot(end) & segm;
-                    if (end) {
-                        const uint32_t code = v >> (2 * l);
-                        const int s = a.lg - l;
-                        const uint32_t idx = (hm_compact7(code >> 1) << s) | hm_compact7(code);
-                        const uint64_t p = q + hm_mbcnt(bal);
-                        if (p < a.out.capacity) {
-                            a.out.keys[p] = hm_cell_key(a.Z - l, coord, s, idx);
-                            a.out.counts[p] = (uint64_t)(j - start + 1);
-                        }
-                    }
-                    q += (uint64_t)__popcll(bal);
-                }
-            }
         }
         while (m) {
             const int i = __builtin_ctzll(m);
@@ -4700,19 +4033,6 @@ void hm_launch_project(hipStream_t s, const double* lat, const double* lon, int6
                        err_word, slow);
 }
 
-static uint32_t hm_cu_count()
-{
-    static int cus = 0;   /* every device of a node is the same part */
-    if (cus <= 0) {
-        int dev = 0, c = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-            c <= 0)
-            c = 256;
-        cus = c;
-    }
-    return (uint32_t)cus;
-}
-
 void hm_launch_part1(hipStream_t s, const HmPart1Args& a0, uint32_t grid, bool out16, int mode)
 {
     if (grid == 0) return;
@@ -4723,49 +4043,30 @@ void hm_launch_part1(hipStream_t s, const HmPart1Args& a0, uint32_t grid, bool o
     HmPart1Args a = a0;
     a.tile0 = 0;
 #define HM_P1_CASE(T, M, FL, G) hipLaunchKernelGGL((k_project_partition<T, M, FL>), dim3(G), b, 0, s, a)
-#define HM_P1_MODES(T, FL, G)                      \
-    do {                                           \
-        if (mode == 0) HM_P1_CASE(T, 0, FL, G);    \
-        else if (mode == 1) HM_P1_CASE(T, 1, FL, G); \
-        else HM_P1_CASE(T, 2, FL, G);              \
+#define HM_P1_MODES(T, G)                             \
+    do {                                              \
+        if (mode == 0) HM_P1_CASE(T, 0, false, G);    \
+        else if (mode == 1) HM_P1_CASE(T, 1, false, G); \
+        else HM_P1_CASE(T, 2, false, G);              \
     } while (0)
-    /* whole pairs of 12288-point tiles through the persistent k_l1_ws (one
-     * block per CU); they end on a k_l1_fast tile boundary, t0 */
-    uint32_t t0 = 0;
-    /* (keep-less calls only: with the keep bytes prefetched too the compute
-     * waves pass 128 VGPRs and spill) */
-    if (HM_L1_WS && HM_L1_FAST && mode == 0 && !a0.keep && full && (int64_t)full == a0.n / HM_T1) {
-        const uint32_t m = HM_WS_UNIT * (uint32_t)(a0.n / (HM_WS_UNIT * (int64_t)HM_TW));
-        if (m) {
-            /* a multiple of HM_L1_SHARDS blocks (or one block per tile): the
-             * shard of a tile, block & 7 = tile & 7, is then fixed by the tile,
-             * as a region overflow's exact re-run needs */
-            const uint32_t cus = std::max<uint32_t>(hm_cu_count() & ~(uint32_t)(HM_L1_SHARDS - 1), HM_L1_SHARDS);
-            const dim3 g(m <= cus ? m : cus);
-            const dim3 bw(HM_WS_THREADS);
-            if (out16) hipLaunchKernelGGL((k_l1_ws<uint16_t, false>), g, bw, 0, s, a, m);
-            else hipLaunchKernelGGL((k_l1_ws<uint32_t, false>), g, bw, 0, s, a, m);
-            t0 = (uint32_t)((uint64_t)m * HM_TW / HM_T1);
-        }
-    }
-    if (full > t0) {
-        a.tile0 = t0;
-        const uint32_t nf = full - t0;
-        if (mode == 0 && HM_L1_FAST) {
+    /* whole tiles: k_l1_fast, or the fused-exact re-run through
+     * k_project_partition (mode 2; mode 1 has no whole tiles) */
+    if (full) {
+        if (mode == 0) {
             if (out16) {
-                if (a.keep) hipLaunchKernelGGL((k_l1_fast<uint16_t, true>), dim3(nf), b, 0, s, a);
-                else hipLaunchKernelGGL((k_l1_fast<uint16_t, false>), dim3(nf), b, 0, s, a);
+                if (a.keep) hipLaunchKernelGGL((k_l1_fast<uint16_t, true>), dim3(full), b, 0, s, a);
+                else hipLaunchKernelGGL((k_l1_fast<uint16_t, false>), dim3(full), b, 0, s, a);
             } else {
-                if (a.keep) hipLaunchKernelGGL((k_l1_fast<uint32_t, true>), dim3(nf), b, 0, s, a);
-                else hipLaunchKernelGGL((k_l1_fast<uint32_t, false>), dim3(nf), b, 0, s, a);
+                if (a.keep) hipLaunchKernelGGL((k_l1_fast<uint32_t, true>), dim3(full), b, 0, s, a);
+                else hipLaunchKernelGGL((k_l1_fast<uint32_t, false>), dim3(full), b, 0, s, a);
             }
-        } else if (out16) HM_P1_MODES(uint16_t, true, nf);
-        else HM_P1_MODES(uint32_t, true, nf);
+        } else if (out16) HM_P1_CASE(uint16_t, 2, true, full);
+        else HM_P1_CASE(uint32_t, 2, true, full);
     }
     if (grid > full) {
         a.tile0 = full;
-        if (out16) HM_P1_MODES(uint16_t, false, grid - full);
-        else HM_P1_MODES(uint32_t, false, grid - full);
+        if (out16) HM_P1_MODES(uint16_t, grid - full);
+        else HM_P1_MODES(uint32_t, grid - full);
     }
 #undef HM_P1_MODES
 #undef HM_P1_CASE
@@ -5168,7 +4469,7 @@ void hm_launch_project_keys(hipStream_t s, const HmPkArgs& a)
 void hm_launch_partN(hipStream_t s, const HmPartNArgs& a, uint32_t items, bool out16, bool few_runs)
 {
     if (items == 0) return;
-    if (few_runs && HM_K2_FR) {
+    if (few_runs) {
         if (out16)
             hipLaunchKernelGGL(k_partition_fr<uint16_t>, hm_grid2(items), dim3(HM_FR_THREADS), 0, s, a);
         else
@@ -5243,26 +4544,12 @@ void hm_launch_aggregate(hipStream_t s, const HmAggArgs& a, uint32_t items, uint
 }
 /* HM_SPW_GRID blocks is 8 waves per SIMD, more than is resident of the
  * kernels holding > 96 SGPRs or > 64 VGPRs (k_small_pairs 7, k_small_sort 5,
- * k_small_emit 4).  HM_SPW_RESIDENT=1 launches only the blocks that fit at
- * once; measured slower (profiles/r6/small_grid_ab.jsonl: hotspot aggregation
- * +50 us, z6-21 +150 us, skew no better): k_small_sort / k_small_emit map
- * buckets to waves statically, and the blocks of the second round that start
- * as the first ones drain even out their uneven shares. */
-template <typename K>
-static uint32_t hm_spw_grid(K kernel, int& cache, uint32_t wb)
-{
-    uint32_t g = HM_SPW_GRID;
-    if (HM_SPW_RESIDENT) {
-        if (cache <= 0) {
-            int per = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kernel, HM_SPW_THREADS, 0) != hipSuccess || per <= 0)
-                per = HM_SPW_GRID / 256;
-            cache = per;
-        }
-        g = (uint32_t)cache * hm_cu_count();
-    }
-    return wb < g ? wb : g;
-}
+ * k_small_emit 4).  A grid of only the resident blocks measured slower
+ * (profiles/r6/small_grid_ab.jsonl: hotspot aggregation +50 us, z6-21 +150 us,
+ * skew no better): k_small_sort / k_small_emit map buckets to waves statically,
+ * and the blocks of the second round that start as the first ones drain even
+ * out their uneven shares. */
+static uint32_t hm_spw_grid(uint32_t wb) { return wb < HM_SPW_GRID ? wb : HM_SPW_GRID; }
 
 void hm_launch_small(hipStream_t s, const HmAggArgs& a, uint64_t* partial)
 {
@@ -5276,28 +4563,19 @@ void hm_launch_small(hipStream_t s, const HmAggArgs& a, uint64_t* partial)
     while (b.spbatch < 64 && (uint64_t)b.spbatch * waves < a.B.count) b.spbatch <<= 1;
     const uint32_t per_block = b.spbatch * (HM_SPW_THREADS / 64);
     const uint32_t wb = (a.B.count + per_block - 1) / per_block;
-    static int occ[5];
-    const dim3 t(HM_SPW_THREADS);
-    if (HM_SP_FUSED) {
-        /* block batches from a counter: a grid of what fits, plus spare blocks
-         * that find the counter spent */
-        const uint32_t bb = b.spbatch * HM_SPP_WAVES;
-        const uint32_t nbb = (a.B.count + bb - 1) / bb;
-        const uint32_t gp = HM_SPW_GRID * (HM_SPW_THREADS / 64) / HM_SPP_WAVES;
-        hipLaunchKernelGGL(k_small_pairs<HM_SPP_WAVES>, dim3(nbb < gp ? nbb : gp), dim3(64 * HM_SPP_WAVES), 0, s, b);
-    }
-    hipLaunchKernelGGL((k_small_sort<0, HM_SPW_SPLIT>), dim3(hm_spw_grid(k_small_sort<0, HM_SPW_SPLIT>, occ[1], wb)), t,
-                       0, s, b);
-    if (HM_SPW_MAX > HM_SPW_SPLIT)
-        hipLaunchKernelGGL((k_small_sort<HM_SPW_SPLIT, HM_SPW_MAX>),
-                           dim3(hm_spw_grid(k_small_sort<HM_SPW_SPLIT, HM_SPW_MAX>, occ[2], wb)), t, 0, s, b);
+    const dim3 t(HM_SPW_THREADS), g(hm_spw_grid(wb));
+    /* k_small_pairs: block batches from a counter: a grid of what fits, plus
+     * spare blocks that find the counter spent */
+    const uint32_t bb = b.spbatch * HM_SPP_WAVES;
+    const uint32_t nbb = (a.B.count + bb - 1) / bb;
+    const uint32_t gp = HM_SPW_GRID * (HM_SPW_THREADS / 64) / HM_SPP_WAVES;
+    hipLaunchKernelGGL(k_small_pairs<HM_SPP_WAVES>, dim3(nbb < gp ? nbb : gp), dim3(64 * HM_SPP_WAVES), 0, s, b);
+    hipLaunchKernelGGL((k_small_sort<0, HM_SPW_SPLIT>), g, t, 0, s, b);
+    if (HM_SPW_MAX > HM_SPW_SPLIT) hipLaunchKernelGGL((k_small_sort<HM_SPW_SPLIT, HM_SPW_MAX>), g, t, 0, s, b);
     hm_launch_scan(s, b.spcnt, b.B.count, partial, (uint64_t*)b.spoff, b.sptotal);
     hipLaunchKernelGGL(k_small_reserve, dim3(1), dim3(64), 0, s, b);
-    hipLaunchKernelGGL((k_small_emit<0, HM_SPW_SPLIT>), dim3(hm_spw_grid(k_small_emit<0, HM_SPW_SPLIT>, occ[3], wb)), t,
-                       0, s, b);
-    if (HM_SPW_MAX > HM_SPW_SPLIT)
-        hipLaunchKernelGGL((k_small_emit<HM_SPW_SPLIT, HM_SPW_MAX>),
-                           dim3(hm_spw_grid(k_small_emit<HM_SPW_SPLIT, HM_SPW_MAX>, occ[4], wb)), t, 0, s, b);
+    hipLaunchKernelGGL((k_small_emit<0, HM_SPW_SPLIT>), g, t, 0, s, b);
+    if (HM_SPW_MAX > HM_SPW_SPLIT) hipLaunchKernelGGL((k_small_emit<HM_SPW_SPLIT, HM_SPW_MAX>), g, t, 0, s, b);
 }
 void hm_launch_pool(hipStream_t s, const HmPoolArgs& a, uint32_t nparents)
 {

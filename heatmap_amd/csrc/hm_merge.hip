@@ -829,17 +829,13 @@ void hm_launch_mb_gather(hipStream_t s, const HmMbGather& a, bool scatter)
  * reservation per bucket.  The next bucket's cells (<= 4 a thread) are loaded
  * into registers while this one is merged, and its bounds one bucket earlier
  * still, so a block's loads overlap its LDS work.  C32: u32 input counts
- * and (TC32) u32 table counts -- 24 KB, 6 blocks a CU; a sum that carries out
+ * and u32 table counts -- 24 KB, 6 blocks a CU; a sum that carries out
  * of 32 bits sets the overflow flag (the caller's global table takes over). */
-#ifndef HM_MB2_TC32
-#define HM_MB2_TC32 1
-#endif
 #define HM_MB2_PF ((HM_MB2_TS / 2 + HM_MB2_T - 1) / HM_MB2_T)
 template <bool C32>
 __global__ __launch_bounds__(HM_MB2_T) void k_mb_merge2(HmMergeArgs a)
 {
-    constexpr bool TC32 = C32 && HM_MB2_TC32;
-    typedef typename std::conditional<TC32, uint32_t, unsigned long long>::type TC;
+    typedef typename std::conditional<C32, uint32_t, unsigned long long>::type TC;
     __shared__ unsigned long long tk[HM_MB2_TS];
     __shared__ TC tc[HM_MB2_TS];
     constexpr int SPT = HM_MB2_TS / HM_MB2_T, NW = HM_MB2_T / 64, PF = HM_MB2_PF;
@@ -893,7 +889,7 @@ __global__ __launch_bounds__(HM_MB2_T) void k_mb_merge2(HmMergeArgs a)
             for (int probes = 0;; probes++) {
                 const unsigned long long o = atomicCAS(&tk[sl], (unsigned long long)HMS_EMPTY, (unsigned long long)k);
                 if (o == HMS_EMPTY || o == k) {
-                    if (TC32) {
+                    if (C32) {
                         if (atomicAdd((uint32_t*)&tc[sl], (uint32_t)c) + (uint32_t)c < (uint32_t)c) full = 1;
                     } else {
                         atomicAdd((unsigned long long*)&tc[sl], (unsigned long long)c);

@@ -73,11 +73,7 @@ __host__ __device__ inline uint32_t hm_l1i(uint32_t d, uint32_t sh) { return sh 
  * and the kernel's own slot s (hot tiles first, then the bank-skewed cold
  * digits), entry [b * HM_D1 + s] = (region base, region capacity, index of
  * the fill word with the shard already chosen, 0); a dead slot is all zero.
- * 196 KB: it stays in L2.  0: every block derives the same from rbase, rcap
- * and smask (rounds 4-6) */
-#ifndef HM_L1_SLOTTAB
-#define HM_L1_SLOTTAB 1
-#endif
+ * 196 KB: it stays in L2. */
 /* levels >= 2 */
 #ifndef HM_PN_THREADS
 #define HM_PN_THREADS 1024
@@ -88,9 +84,6 @@ __host__ __device__ inline uint32_t hm_l1i(uint32_t d, uint32_t sh) { return sh 
 /* level 2 from the level-1 regions (k_partition_fr): keys in registers */
 #ifndef HM_FR_THREADS
 #define HM_FR_THREADS 1024
-#endif
-#ifndef HM_K2_FR
-#define HM_K2_FR 1                          /* 0: k_partition (run streaming), 1: k_partition_fr */
 #endif
 #ifndef HM_FR_GROUP
 #define HM_FR_GROUP 4
@@ -107,9 +100,6 @@ __host__ __device__ inline uint32_t hm_l1i(uint32_t d, uint32_t sh) { return sh 
 #define HM_AG_THREADS 1024
 #define HM_AG_CELLS 16384
 #define HM_AG_LG 7
-#ifndef HM_AG_FAST
-#define HM_AG_FAST 1                        /* k_aggregate: hm_lds_count_fast (merge only wave-heavy keys) */
-#endif
 #ifndef HM_TA
 #define HM_TA (1u << 18)                    /* keys per aggregation work item */
 #endif
@@ -130,28 +120,20 @@ __host__ __device__ inline uint32_t hm_l1i(uint32_t d, uint32_t sh) { return sh 
 #define HM_SPW_SPLIT 512
 #endif
 static_assert(HM_SPW_MAX >= HM_SP_MAX, "every bucket without a dense work item needs the wavefront path");
-/* HM_SP_FUSED: the <= 32-key, <= 4-run small buckets go through ONE fused
- * sort + count + emit kernel (k_small_pairs) instead of k_small_sort, a scan
- * and k_small_emit */
-#ifndef HM_SP_FUSED
-#define HM_SP_FUSED 1
-#endif
+/* the small buckets of <= 32 keys in <= 32 runs or 33-64 keys in <= 64 runs
+ * (hm_sp_fused_ok) go through ONE fused sort + count + emit kernel
+ * (k_small_pairs) instead of k_small_sort, a scan and k_small_emit */
 #define HM_SPW_THREADS 256
 #define HM_SPW_GRID (256 * 8)
 #ifndef HM_SPP_WAVES
 #define HM_SPP_WAVES 4      /* k_small_pairs: waves per block (one cursor reservation per block and round) */
 #endif
-#ifndef HM_SPP_STAGE
-#define HM_SPP_STAGE 1      /* k_small_pairs: cells staged in LDS, written a whole line per instruction */
-#endif
 #ifndef HM_SPP_ROWS
 #define HM_SPP_ROWS 32      /* k_small_pairs: rows (wave passes) per wave and round, <= 32 */
 #endif
 static_assert(HM_SPP_ROWS <= 32, "a row's two cell counts sit in lanes 2p, 2p + 1");
+/* k_small_pairs' cells are staged in LDS and written a whole line per instruction */
 #define HM_SPP_STAGE_CELLS 512   /* >= a row's cells: 2 segments x 32 keys x 7 levels */
-#ifndef HM_SPW_RESIDENT
-#define HM_SPW_RESIDENT 0   /* 1: small-bucket grids of the blocks resident at once (hm_spw_grid; slower) */
-#endif
 #define HM_POOL_THREADS 256
 #define HM_MAX_LEVELS 4
 #define HM_COUNT_MAX_ZOOM 21                /* level-1 keys 2*(Z-5) bits fit u32 */
@@ -266,7 +248,7 @@ struct HmPart1Args {
     const uint32_t* rbase;    /* [HM_D1 * HM_L1_SHARDS] */
     const uint32_t* rcap;     /* [HM_D1 * HM_L1_SHARDS] */
     const uint8_t* smask;     /* [F]: shards of digit d - 1 (0 or HM_L1_SHARDS - 1) */
-    const uint4* l1slot;      /* [HM_L1_SHARDS * HM_D1] k_l1_fast's slot table (HM_L1_SLOTTAB), lat/lon input */
+    const uint4* l1slot;      /* [HM_L1_SHARDS * HM_D1] k_l1_fast's slot table (k_l1_slots), lat/lon input */
     unsigned long long* overflow;
     unsigned long long* err_word;
     HmExotic x;

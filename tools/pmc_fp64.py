@@ -45,7 +45,7 @@ def main():
             continue
         for c in C:
             tot[c] += v.get(c, 0.0)
-            if k.startswith(("void k_l1_fast<", "void k_project_partition<", "void k_l1_ws<")):
+            if k.startswith(("void k_l1_fast<", "void k_project_partition<")):
                 k1[c] += v.get(c, 0.0)
     ops = lambda t: 64.0 * (t["SQ_INSTS_VALU_ADD_F64"] + t["SQ_INSTS_VALU_MUL_F64"] + t["SQ_INSTS_VALU_FMA_F64"] +
                             t["SQ_INSTS_VALU_TRANS_F64"]) / steps / pts   # noqa: E731

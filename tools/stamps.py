@@ -29,16 +29,12 @@ NAMES = {
     "stamps2": ["start", "item+loads_issue+init", "count_rank(loads)", "barrier", "scan+run_atomics", "scatter",
                 "copy+runs"],
     "stamps4": ["start", "issue+lds_setup", "project(loads)", "redo+count_rank", "reserve+scan", "stage", "copy"],
-    "stamps4r6": ["start", "issue+lds_setup", "project(loads)", "redo+count_rank", "reserve+scan", "stage", "copy"],
     "stamps5": ["start", "zero+item", "count(stream_runs)", "squeeze", "pyramid+emit"],
-    "stamps6": [],
-    "stamps6w8": [],
-    "stamps6w10": [],
     "stamps7": [],
     "stamps7noatom": [],
 }[VAR]
 K = len(NAMES)
-n = int(float(os.environ.get("HM_POINTS", "2.5e8" if not VAR.startswith(("stamps6", "stamps7")) else "1e9")))
+n = int(float(os.environ.get("HM_POINTS", "2.5e8" if not VAR.startswith("stamps7") else "1e9")))
 lat = torch.empty(n, dtype=torch.float64, device="cuda")
 lon = torch.empty(n, dtype=torch.float64, device="cuda")
 device.synth(os.environ.get("HM_KIND", "skew" if VAR.startswith("stamps7") else "hotspots"), lat, lon)
@@ -61,25 +57,6 @@ if VAR.startswith("stamps7"):
         print("%-24s per round mean %8.0f  median %8.0f" % (nm, (w[ok, i] / r[:, 0]).mean(), np.median(w[ok, i] / r[:, 0])))
     for i, nm in [(0, "W1 pass 1"), (1, "W1 barrier A wait"), (2, "W1 barrier B wait"), (3, "W1 pass 2")]:
         print("%-24s per round mean %8.0f  median %8.0f" % (nm, (al[ok, i] / r[:, 0]).mean(), np.median(al[ok, i] / r[:, 0])))
-    sys.exit(0)
-if VAR.startswith("stamps6"):
-    # k_l1_ws: per block, phase cycles summed over its tiles; slot 11 = its tiles;
-    # the writer waves' phases in the rows 4096 + block
-    w = st[4096:4096 + 4096, :8]
-    st = st[:4096]
-    ok = st[:, 11] > 0
-    nt = st[ok, 11:12]
-    per = st[ok, :6] / nt
-    perw = w[ok] / nt
-    names = ["C wait+project", "C redo+prefetch+count", "C BAR1 wait", "C scan(3 bar)", "C stage", "C BAR3 wait"]
-    namesw = ["W deltas (atomics)", "W rendezvous", "W copy-out", "W BAR1 wait", "W reserve issue", "W scan(3 bar)",
-              "W zero+BAR3"]
-    print("stamps6 blocks", int(ok.sum()), "tiles/block", nt.mean())
-    for k, nm in enumerate(names):
-        print("%-24s per tile mean %8.0f  median %8.0f" % (nm, per[:, k].mean(), np.median(per[:, k])))
-    for k, nm in enumerate(namesw):
-        print("%-24s per tile mean %8.0f  median %8.0f" % (nm, perw[:, k].mean(), np.median(perw[:, k])))
-    print("C total per tile %.0f, W total per tile %.0f" % (per.sum(1).mean(), perw[:, :7].sum(1).mean()))
     sys.exit(0)
 st_all = st.copy()
 extra = st[:, K:K + 3].copy()

@@ -14,34 +14,19 @@ import sys
 import time
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
 VDIR = os.path.join(REPO, "heatmap_amd", "_lib", "variants")
 
 VARIANTS = {
     "base": [],
-    "nows": ["HM_L1_WS=0"],                  # level 1 through k_l1_fast only (the shipped default)
-    "wslate": ["HM_WS_PREFETCH_LATE=1"],     # k_l1_ws: next tile's loads after the count
-    "spunfused": ["HM_SP_FUSED=0"],          # <= 32-key buckets through k_small_sort / scan / k_small_emit (round 5)
-    "spres": ["HM_SPW_RESIDENT=1"],          # k_small_sort / k_small_emit on grids of their resident blocks
     "agpad4": ["HM_AG_PADW=4u"],             # k_aggregate histogram rows padded by 4 words (8 shipped)
-    "agnostage": ["HM_AG_STAGE=0"],          # hm_reg_pyramid7: per-level cell stores (no LDS staging)
     "spp8": ["HM_SPP_WAVES=8"],              # k_small_pairs: 8-wave blocks
     "sprows16": ["HM_SPP_ROWS=16"],          # k_small_pairs: 16 rows a round (7 blocks per CU with staging)
-    "spnostage": ["HM_SPP_STAGE=0"],         # k_small_pairs: per-level cell stores (no LDS staging)
-    "ws": ["HM_L1_WS=1"],                    # k_l1_ws (12 compute + 4 writer waves)
-    "ws8": ["HM_L1_WS=1", "HM_WS_C=512"],                  # k_l1_ws: 8 compute + 8 writer waves, 8192-point tiles
-    "ws10": ["HM_L1_WS=1", "HM_WS_C=640"],                 # k_l1_ws: 10 compute + 6 writer waves, 10240-point tiles
-    "ws12": ["HM_L1_WS=1", "HM_WS_C=768"],                 # k_l1_ws: 12 compute + 4 writer waves, 12288-point tiles
-    "stamps6w8": ["HM_STAMPS=6", "HM_L1_WS=1", "HM_WS_C=512"],
-    "stamps6w10": ["HM_STAMPS=6", "HM_L1_WS=1", "HM_WS_C=640"],
     "stamps7": ["HM_STAMPS=7"],              # k_small_pairs: per-round phase cycles (worker 0 and the allocator)
     "stamps": ["HM_STAMPS=1"],               # phase stamps for tools/stamps.py (k_partition)
     "stamps1": ["HM_STAMPS=2"],              # k_project_partition
     "stamps2": ["HM_STAMPS=3"],              # k_partition_fr
     "stamps4": ["HM_STAMPS=4"],              # k_l1_fast
     "stamps5": ["HM_STAMPS=5"],              # k_aggregate
-    "stamps6": ["HM_STAMPS=6", "HM_L1_WS=1"],              # k_l1_ws: per-block phase cycles summed over its tiles
-    "l1old": ["HM_L1_FAST=0"],               # level 1 through k_project_partition (round 3)
     "l1m3": ["HM_L1_MERGE_MIN=3"],
     "l1m12": ["HM_L1_MERGE_MIN=12"],
     "l1nomerge": ["HM_L1_MERGE_MIN=65"],
@@ -57,7 +42,6 @@ VARIANTS = {
     "t512_8k": ["HM_PN_THREADS=512"],
     "su2": ["HM_SU=2"],
     "su8": ["HM_SU=8"],
-    "k2old": ["HM_K2_FR=0"],                # level 2 through k_partition (run streaming)
     "p1_1024x8": ["HM_P1_THREADS=1024", "HM_P1_PPT=8"],
     "p1_1024x16": ["HM_P1_THREADS=1024"],
     "p1_1024x8w8": ["HM_P1_THREADS=1024", "HM_P1_PPT=8", "HM_P1_WAVES=8"],
@@ -75,46 +59,34 @@ VARIANTS = {
     "sp1024": ["HM_SP_MAX=1024"],           # buckets of 1025-2048 keys to k_aggregate
     "sp512": ["HM_SP_MAX=512"],             # buckets of 513-2048 keys to k_aggregate
     "sp256": ["HM_SP_MAX=256", "HM_SPW_SPLIT=256"],   # buckets of 257-2048 keys to k_aggregate
-    "agslow": ["HM_AG_FAST=0"],             # k_aggregate with the lane-0 merge on every key
     "agm4": ["HM_MERGE_MIN=4"],
     "agm16": ["HM_MERGE_MIN=16"],
     "ta512k": ["HM_TA=524288"],
     "ta1m": ["HM_TA=1048576"],
     "hot1k": ["HM_MAX_HOT=1024"],
     "hot1kta1m": ["HM_MAX_HOT=1024", "HM_TA=1048576"],
-    "os8": ["HM_OS_IT=8"],
-    "tn16k": ["HM_TN=16384"],
+    "os8": ["HM_OS_IT=8"],                  # one-sweep radix tiles of 2048 keys (4 blocks per CU)
+    "tn16k": ["HM_TN=16384"],               # 16K-key partition items (half the (item, child) pairs)
     "os24": ["HM_OS_IT=24"],                # one-sweep radix tiles of 6144 keys
     "os32": ["HM_OS_IT=32"],                # one-sweep radix tiles of 8192 keys
-    "l1n6": ["HM_L1_NARROW=1", "HM_L1_WAVES=6"],   # k_l1_fast with 4-B staging, 3 blocks per CU (spills)
-    "nofuse": ["HM_CS_FUSE=0"],                      # packed grouped records: one zoom step per cascade launch
     "cs2it8": ["HM_CS2_IT=8"],                       # k_cascade2: 2048-item tiles
     "cs2it12": ["HM_CS2_IT=12"],
-    "l1nt0": ["HM_L1_NT=0"],                        # K1's point loads without the non-temporal hint
-    "l1early": ["HM_L1_LATE_DEST=0"],
-    # k_l1_fast's serial chains (round 7): each change off on its own, and both off (round 6's kernel)
-    "l1noslottab": ["HM_L1_SLOTTAB=0"],             # every block derives its slots' regions from rbase / rcap / smask
-    "l1nocopybatch": ["HM_L1_COPY_BATCH=0"],        # copy-out: entry and delta reads per key
-    "l1r6": ["HM_L1_SLOTTAB=0", "HM_L1_COPY_BATCH=0"],
-    "stamps4r6": ["HM_STAMPS=4", "HM_L1_SLOTTAB=0", "HM_L1_COPY_BATCH=0"],
     "sh8": ["HM_L1_SHARD_TILES=8"],                 # level-1 digits sharded above 8 tiles of points (default 64)
     "sh2": ["HM_L1_SHARD_TILES=2"],
     "lb1": ["HM_OS_LB=1"],                           # one-sweep look-back: one predecessor per round trip
     "lb8": ["HM_OS_LB=8"],
     "sh4": ["HM_L1_SHARD_TILES=4"],
-    "sh16": ["HM_L1_SHARD_TILES=16"],                # K1: destinations before the staging (round 4)
+    "sh16": ["HM_L1_SHARD_TILES=16"],
     "xr16": ["HM_XR_PPT=16"],                        # route scatter: 4096-cell tiles (default 2048)
     "xr4": ["HM_XR_PPT=4"],
     "xrc8": ["HM_XRC_PPT=8"],                        # route count: 8 cells a thread in flight (default 16)
     "mg16": ["HM_MG_PPT=16"],                        # k_mb_gather: 4096-cell tiles (default 2048)
     "mg4": ["HM_MG_PPT=4"],
     "mgc32": ["HM_MG_CHUNK=32768"],                   # 32K-cell chunks a block (default 16K)
-    "mbtc64": ["HM_MB2_TC32=0"],                    # k_mb_merge2: u64 table counts
     "mb2k": ["HM_MB2_TS=2048", "HM_MB2_T=256"],      # k_mb_merge2 tables / block size (default 4096 / 512)
     "mb8k": ["HM_MB2_TS=8192", "HM_MB2_T=1024"],
     "mb4k256": ["HM_MB2_TS=4096", "HM_MB2_T=256"],
     "mb4k1024": ["HM_MB2_TS=4096", "HM_MB2_T=1024"],
-    "l1n4": ["HM_L1_NARROW=1", "HM_L1_WAVES=4"],   # 4-B staging at 2 blocks per CU               # 16K-key partition items (half the (item, child) pairs)                  # one-sweep radix tiles of 2048 keys (4 blocks per CU)
 }
 
 # Timing-only experiments: text patches applied to a copy of the sources (the
@@ -125,20 +97,19 @@ PATCHES = {
     # k_partition / k_aggregate run bodies: no global key loads
     "noload": [("hm_kernels.hip", "                        x[u] = kv[L.bv[r] + (v - L.pre[r])];",
                 "                        x[u] = make_uint4(v, v * 3u, v * 5u, v * 7u);")],
-    # level 1: no region reservation atomics (every tile writes at its region base)
-    "noatom1": [("hm_kernels.hip", "if (d < F && cnt[q]) gpos[q] = atomicAdd(&a.fill[slot[q]], cnt[q]);",
-                 "if (d < F && cnt[q]) gpos[q] = 0;")],
 }
 # k_l1_fast (level 1, whole tiles): compute without the point loads, loads
 # without the key stores, and no region reservation atomics
-PATCHES["l1noload"] = [("hm_kernels.hip", """            la[k] = lat2[k * HM_P1_THREADS + tid];
-            lo[k] = lon2[k * HM_P1_THREADS + tid];""", """            la[k] = make_double2(40.0 + 1e-7 * (double)(tid + 1024 * k), 40.0 + 1.3e-7 * (double)(tid + 1024 * k));
+PATCHES["l1noload"] = [("hm_kernels.hip", """            la[k] = hm_stream_load2(lat2 + k * HM_P1_THREADS + tid);
+            lo[k] = hm_stream_load2(lon2 + k * HM_P1_THREADS + tid);""", """            la[k] = make_double2(40.0 + 1e-7 * (double)(tid + 1024 * k), 40.0 + 1.3e-7 * (double)(tid + 1024 * k));
             lo[k] = make_double2(-122.0 + 1e-7 * (double)(tid + 1024 * k), -122.0 + 1.7e-7 * (double)(tid + 1024 * k));""")]
 PATCHES["l1nostore"] = [
     ("hm_kernels.hip", "auto put_cold = [&](uint2 e) { *(OutT*)(outb + (uint64_t)e.y * sizeof(OutT)) = (OutT)e.x; };",
      "auto put_cold = [&](uint2 e) { if (e.x == 0xFFFFFFFFu && e.y == 0x1234567u) *(OutT*)outb = (OutT)e.x; };"),
-    ("hm_kernels.hip", "        *(uint16_t*)(houtb + (uint64_t)e.y * 2u) = (uint16_t)hk;",
-     "        if (hk == 0xFFFFFFFFu && e.y == 0x1234567u) *(uint16_t*)houtb = (uint16_t)hk;")]
+    ("hm_kernels.hip", "        if (hot32) *(uint32_t*)(houtb + (uint64_t)e.y * 4u) = hk;",
+     "        if (hot32) { if (hk == 0xFFFFFFFFu && e.y == 0x1234567u) *(uint32_t*)houtb = hk; }"),
+    ("hm_kernels.hip", "        else *(uint16_t*)(houtb + (uint64_t)e.y * 2u) = (uint16_t)hk;",
+     "        else if (hk == 0xFFFFFFFFu && e.y == 0x1234567u) *(uint16_t*)houtb = (uint16_t)hk;")]
 PATCHES["l1noatom"] = [("hm_kernels.hip", "        if (cnt[q]) gpos[q] = atomicAdd(&a.fill[st[q].z], cnt[q]);",
                         "        if (cnt[q]) gpos[q] = 0;")]
 # k_small_pairs timing builds: no cursor atomic (a made-up base), no cell
@@ -153,9 +124,8 @@ PATCH_DEFINES["stamps7noatom"] = ["HM_STAMPS=7"]
 PATCHES["sp8w16"] = [("hm_kernels.hip", "__global__ __launch_bounds__(64 * NWB) void k_small_pairs(HmAggArgs a)",
                       "__global__ __launch_bounds__(64 * NWB) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_small_pairs(HmAggArgs a)")]
 PATCH_DEFINES["sp8w16"] = ["HM_SPP_ROWS=16"]
-PATCHES["spnostore"] = [("hm_kernels.hip", """            const uint64_t pos = q + hm_mbcnt(bal);
-            if (pos < a.out.capacity) {""", """            const uint64_t pos = q + hm_mbcnt(bal);
-            if (pos == 0x123456789ull) {""")]
+PATCHES["spnostore"] = [("hm_kernels.hip", "        if (i < n && p < a.out.capacity) {",
+                         "        if (i < n && p == 0x123456789ull && p < a.out.capacity) {")]
 # levels 2.. always on the spread plan (3 zooms per level) when no tile is hot
 PATCHES["spreadall"] = [("hm_api.cpp", "spread_replan(ctx->host_aux, F, (double)n, zb, zs, &L, ctx->spread_min_keys, true);",
                          "spread_replan(ctx->host_aux, F, (double)n, zb, zs, &L, ctx->spread_min_keys, false);")]
@@ -167,29 +137,28 @@ PATCHES["l1occ1"] = [("hm_kernels.hip", """    __shared__ uint32_t s_over;
     /* the polynomial table plus one poison row""")]
 # the exchange's bucket merge (k_mb_merge2): no LDS insertion atomics (each
 # key stored at its home slot), or no output stores
-PATCHES["mb2noins"] = [("hm_merge.hip", """                        const unsigned long long o =
-                            atomicCAS(&tk[sl], (unsigned long long)HMS_EMPTY, (unsigned long long)k[j]);""",
-                        """                        tk[sl] = k[j];
-                        const unsigned long long o = k[j];""")]
+PATCHES["mb2noins"] = [("hm_merge.hip", """            for (int probes = 0;; probes++) {
+                const unsigned long long o = atomicCAS(&tk[sl], (unsigned long long)HMS_EMPTY, (unsigned long long)k);""",
+                        """            for (int probes = 0;; probes++) {
+                tk[sl] = k;
+                const unsigned long long o = k;""")]
 PATCHES["mb2nowrite"] = [("hm_merge.hip", """                    if (q < a.cap) {
                         a.keys_out[q] = tk[sl];
-                        a.counts_out[q] = tc[sl];
-                    }""", """                    if (q == 0x123456789ull) {
+                        a.counts_out[q] = (uint64_t)tc[sl];
+                    }""", """                    if (q == 0x123456789ull && q < a.cap) {
                         a.keys_out[q] = tk[sl];
-                        a.counts_out[q] = tc[sl];
+                        a.counts_out[q] = (uint64_t)tc[sl];
                     }""")]
 PATCHES["mb2nocur"] = [("hm_merge.hip", "if (lane == 63) sbase = inc ? atomicAdd(a.cursor, (unsigned long long)inc) : 0ull;",
                         "if (lane == 63) sbase = (uint64_t)b * 1024u;")]
-PATCHES["mb2loadonly"] = [("hm_merge.hip", """                for (int j = 0; j < 4; j++) {
-                    if (k[j] == HMS_EMPTY) continue;
-                    const uint64_t h = hms_hash(k[j]);""", """                for (int j = 0; j < 4; j++) {
-                    if (k[j] != 0x1234567ull) continue;
-                    const uint64_t h = hms_hash(k[j]);""")]
+PATCHES["mb2loadonly"] = [("hm_merge.hip", """            if (k == HMS_EMPTY) return;
+            const uint64_t h = hms_hash(k);""", """            if (k != 0x1234567ull) return;
+            const uint64_t h = hms_hash(k);""")]
 # one-sweep radix passes without the decoupled look-back (timing only: wrong offsets)
 PATCHES["rxnolb"] = [("hm_general.hip", """        for (int64_t p = (int64_t)tile - 1; p >= 0;) {
-            const uint64_t wv = __hip_atomic_load(a.tstat + (uint64_t)p * 256 + d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);""",
+            uint64_t wv[HM_OS_LB];""",
                       """        for (int64_t p = (int64_t)tile - 1; p >= 0 && p == 0x7FFFFFFFFFFF;) {
-            const uint64_t wv = __hip_atomic_load(a.tstat + (uint64_t)p * 256 + d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);""")]
+            uint64_t wv[HM_OS_LB];""")]
 # k_aggregate: multi-item buckets without their global histogram adds (timing only)
 PATCHES["agnoslot"] = [("hm_kernels.hip", "            if (i < ncell && x[k]) atomicAdd(&g[i], x[k]);",
                         "            if (i < ncell && x[k] == 0xFFFFFFFFu) atomicAdd(&g[i], x[k]);")]
@@ -223,16 +192,6 @@ PATCHES["l1stagall"] = [("hm_kernels.hip", """    const int64_t base = (a.tile0 
     HM_STAMP_M(4, 0);
     if (blockIdx.x < 512)
         for (int z = 0; z < (int)(blockIdx.x & 7); z++) __builtin_amdgcn_s_sleep(127);""")]
-# k_aggregate's count without any wave merging: one plain LDS atomic per key
-PATCHES["agplain"] = [("hm_kernels.hip", """            if (HM_AG_FAST)
-                hm_lds_count_fast(grid, dummy + (uint32_t)hm_lane(), sl(k), v);
-            else
-                hm_lds_count(grid, dummy, sl(k), v);""", """            atomicAdd(&grid[v ? sl(k) : dummy + (uint32_t)hm_lane()], 1u);""")]
-# k_small_emit's pair path (<= 32-key buckets, the skew cloud's background) without its cell stores (timing only)
-PATCHES["emnostore"] = [("hm_kernels.hip", """                        if (p < a.out.capacity) {
-                            a.out.keys[p] = hm_cell_key(a.Z - l, coord, s, idx);""", """                        if (p == 0x123456789ull) {
-                            a.out.keys[p] = hm_cell_key(a.Z - l, coord, s, idx);""")]
-# compile-time macros added to a patched build
 
 
 def build(names):
@@ -346,6 +305,7 @@ def merge_one(name, points, steps):
 
 
 def main():
+    sys.path.insert(0, REPO)
     cmd = sys.argv[1]
     names = sys.argv[2:] or ["base"]
     if cmd == "build":
