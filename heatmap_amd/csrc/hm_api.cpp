@@ -2838,8 +2838,12 @@ extern "C" int hm_stream_add(hm_stream* s, const double* lat, const double* lon,
                              const uint32_t* hour, const uint32_t* group, int64_t n)
 {
     if (!s || n < 0 || (n > 0 && (!lat || !lon)) || n >= (int64_t)0xFFFFFFF0ll) return HM_E_ARG;
-    if (n == 0) return HM_OK;
     hm_ctx* ctx = s->ctx;
+    /* hm_last_error is this call's: a batch of a few buckets is counted on
+     * helper contexts and would leave an earlier call's error standing */
+    ctx->last_err_index = -1;
+    ctx->last_err_kind = HM_OK;
+    if (n == 0) return HM_OK;
     HIPCHK(hipSetDevice(ctx->device));
     hipStream_t q = ctx->stream;
     int st;
@@ -2890,7 +2894,20 @@ extern "C" int hm_stream_add(hm_stream* s, const double* lat, const double* lon,
     const uint32_t lo = (uint32_t)s->hstate[HMS_ST_BMM];
     const unsigned long long e = s->hstate[HMS_ST_ERR];
     if (e != ~0ull) {
-        ctx->last_err_index = (int64_t)(e >> 8);
+        /* a kept point with a bad hour.  A point before it that does not
+         * project is the batch's first failing point (input order, as
+         * hm_count's).  Error path only, so the batch simply goes through one
+         * more whole hm_count with no room for cells: it ends in a point's
+         * error, or in HM_OK / HM_E_CAPACITY when every point projects (then
+         * the hour is the error).  A failure of that call itself (memory,
+         * HIP) is returned as it is. */
+        const int64_t hi = (int64_t)(e >> 8);
+        int64_t m2 = 0, nx2 = 0;
+        const int st2 = hm_count(ctx, lat, lon, keep, n, s->zmin, s->zmax, nullptr, nullptr, 0, &m2, nullptr, 0, &nx2);
+        const bool point = st2 == HM_E_NAN || st2 == HM_E_DOMAIN || st2 == HM_E_INF || st2 == HM_E_RANGE;
+        if (point && ctx->last_err_index >= 0 && ctx->last_err_index < hi) return st2;
+        if (!point && st2 != HM_OK && st2 != HM_E_CAPACITY) return st2;
+        ctx->last_err_index = hi;
         ctx->last_err_kind = (int)(e & 0xFF);
         return ctx->last_err_kind;
     }

@@ -37,12 +37,31 @@ def _torch():
     return torch
 
 
+class _Calls:
+    """The library as a context calls it: fetching any entry point but those
+    that only read the last call's results or set the context up starts a
+    new call, which ends the rebased error index a failed chunked count left
+    on the context (Context.chunk_error).  Every caller that goes through
+    ctx.L is covered, wrappers, tools and tests alike."""
+
+    KEEP = ("hm_last_error", "hm_last_stats", "hm_ctx_set_stream", "hm_ctx_tune", "hm_ctx_destroy")
+
+    def __init__(self, ctx, lib):
+        self._ctx, self._lib = ctx, lib
+
+    def __getattr__(self, name):
+        if name not in self.KEEP:
+            self._ctx.chunk_error = None
+        return getattr(self._lib, name)
+
+
 class Context:
     """One hm_ctx per (device, host thread)."""
 
     def __init__(self, device: int = 0):
         torch = _torch()
-        self.L = _lib.load()
+        self.chunk_error = None   # (input index, kind) of the failing point of a chunked count
+        self.L = _Calls(self, _lib.load())
         self.device = device
         p = ctypes.c_void_p()
         with torch.cuda.device(device):
@@ -59,6 +78,11 @@ class Context:
             self._bound = h
 
     def last_error(self):
+        """(index, kind) of the last call's first failing point, (-1, 0) if
+        none; after a chunked count the index is the input's, not the
+        chunk's (_count_chunked)."""
+        if self.chunk_error is not None:
+            return self.chunk_error
         idx = ctypes.c_int64(-1)
         kind = ctypes.c_int(0)
         self.L.hm_last_error(self.ptr, ctypes.byref(idx), ctypes.byref(kind))
@@ -277,10 +301,16 @@ def _count_chunked(a, b, kp, n, zmin, zmax, device, tiles, chunk):
         try:
             m, buf = count_device(a[s:e], b[s:e], None if kp is None else kp[s:e], zmin, zmax, device,
                                   tiles=tiles, chunk=chunk)
-        except _lib.DevicePathUnsupported as ex:
-            idx, _ = ctx.last_error()
-            raise _lib.DevicePathUnsupported(str(ex).split(" (point")[0] +
-                                             ("" if idx < 0 else " (point %d)" % (idx + s))) from None
+        except (ValueError, OverflowError, _lib.DevicePathUnsupported) as ex:
+            # the library reports the chunk's index: hm_last_error and the
+            # message carry the input's
+            idx, kind = ctx.last_error()
+            if idx < 0:
+                raise
+            ctx.chunk_error = (idx + s, kind)
+            if not isinstance(ex, _lib.DevicePathUnsupported):
+                raise
+            raise _lib.DevicePathUnsupported(str(ex).split(" (point")[0] + " (point %d)" % (idx + s)) from None
         keys.append(buf.keys[:m].clone())
         counts.append(buf.counts[:m].clone())
         if buf.nx:

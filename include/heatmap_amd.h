@@ -65,7 +65,20 @@ extern "C" {
                             zoom-0 tile row outside [-16, 16) / column outside
                             [-2^47, 2^47).  (Latitudes of any magnitude are
                             projected: glibc's Payne-Hanek reduction is
-                            restated, csrc/hm_branred.h.) */
+                            restated, csrc/hm_branred.h.)  A call that holds
+                            both a point the reference rejects and a point
+                            beyond these tile fields reports one of the two:
+                            a count made by hm_count's level pipeline (also
+                            for hm_stream_add, which counts a batch of up to
+                            64 (group, hour) buckets with hm_count) projects
+                            every point before any key is built and reports
+                            the reference's error; hm_count's general path,
+                            hm_count_grouped*, and hm_stream_add for larger
+                            batches take one minimum over both kinds and
+                            report whichever point comes first.
+                            hm_stream_add: also a kept point whose hour lies
+                            outside [base_hour, base_hour + 2^28), ranked
+                            with the projection errors by input order. */
 #define HM_E_EXOTIC 9    /* hm_stream_add only: a kept point whose zoom-zmax tile
                             lies outside [0, 2^zmax)^2 (|lat| > 85.0511..., or
                             lon outside [-180, 180)); the resident table's keys
