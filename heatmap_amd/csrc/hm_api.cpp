@@ -69,7 +69,7 @@ struct hm_ctx {
     int64_t last_err_index = -1;
     int last_err_kind = 0;
     int64_t last_slow = 0;
-    double stage_us[8] = {0};
+    double stage_us[9] = {0};              /* [8]: keys per aggregation work item (0: general path) */
     hipEvent_t ev[HM_NEV];
     /* plan-tuning knobs, read once from the environment at hm_ctx_create
      * (INTEGRATION.md): HM_SPREAD_MIN_KEYS, HM_RS_BIG_MIN */
@@ -343,6 +343,15 @@ int hm_ctx_tune(hm_ctx* c, const char* name, double value, double* old)
         if (value > 5) return HM_E_ARG;
         prev = c->run_shard_bits;
         c->run_shard_bits = value < 0 ? -1 : (int)value;
+    } else if (!strcmp(name, "HM_TA_MIN")) {
+        const uint32_t v = (value >= 1024 && value <= (double)HM_TA) ? (uint32_t)value : 0u;
+        if (!v || (double)v != value || (v & (v - 1))) return HM_E_ARG;
+        prev = c->ta_min;
+        c->ta_min = v;
+    } else if (!strcmp(name, "HM_TA_ITEMS")) {
+        if (!(value >= 1 && value <= 4294967295.0)) return HM_E_ARG;
+        prev = c->ta_items;
+        c->ta_items = (uint32_t)value;
     } else {
         return HM_E_ARG;
     }
@@ -397,7 +406,7 @@ int hm_last_stats(hm_ctx* c, int64_t* slow_points, double* stage_us, int n_stage
 {
     if (!c) return HM_E_ARG;
     if (slow_points) *slow_points = c->last_slow;
-    for (int i = 0; i < n_stages && i < 8; i++) stage_us[i] = c->stage_us[i];
+    for (int i = 0; i < n_stages && i < 9; i++) stage_us[i] = c->stage_us[i];
     if (n_stages > 7) stage_us[7] = (double)c->last_levels;
     return HM_OK;
 }
@@ -672,7 +681,7 @@ static int count_fallback(hm_ctx* ctx, const double* lat, const double* lon, con
     *nx_out = (int64_t)ctx->host_state[ST_XCURSOR];
     ctx->last_slow = 0;
     ctx->last_levels = 0;
-    for (int i = 0; i < 8; i++) ctx->stage_us[i] = 0;
+    for (int i = 0; i < 9; i++) ctx->stage_us[i] = 0;
     return (*n_out > capacity || *nx_out > xcapacity) ? HM_E_CAPACITY : HM_OK;
 }
 
@@ -753,12 +762,13 @@ static int count_impl(hm_ctx* ctx, const double* lat, const double* lon, const i
      * record is an API call, and small calls (stream batches) are bound by
      * the host's issue rate */
     const bool timing = n >= (1ll << 24) && ctx->stage_timing;
-    /* keys per aggregation work item: HM_TA, halved (down to 16K) until the
-     * call has >= 512 items' worth of points -- a 1e7-point call otherwise
-     * runs ~40 items on 256 CUs */
+    /* keys per aggregation work item: HM_TA, halved (down to HM_TA_MIN, 16K)
+     * until the call has >= HM_TA_ITEMS (128) items' worth of points -- a
+     * 1e7-point call otherwise runs ~40 items on 256 CUs */
     uint32_t ta = HM_TA;
     while (ta > ctx->ta_min && (uint64_t)n < (uint64_t)ta * ctx->ta_items) ta >>= 1;
-    for (int i = 0; i < 8; i++) ctx->stage_us[i] = 0;
+    for (int i = 0; i < 9; i++) ctx->stage_us[i] = 0;
+    ctx->stage_us[8] = (double)ta;          /* hm_last_stats: keys per aggregation work item */
     ctx->last_levels = L;
 
     /* level 1 reads the input in HM_T1-point tiles; points the fast path

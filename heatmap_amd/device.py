@@ -90,8 +90,8 @@ class Context:
 
     def last_stats(self):
         slow = ctypes.c_int64(0)
-        us = (ctypes.c_double * 8)()
-        self.L.hm_last_stats(self.ptr, ctypes.byref(slow), us, 8)
+        us = (ctypes.c_double * 9)()
+        self.L.hm_last_stats(self.ptr, ctypes.byref(slow), us, 9)
         return slow.value, list(us)
 
     def tune(self, name: str, value: float) -> float:

@@ -136,6 +136,11 @@ int hm_ctx_destroy(hm_ctx* ctx);
  *   HM_HOT_MIN_KEYS     ... and >= this many estimated points (default 65536)
  *   HM_RUN_SHARD_BITS   log2 run counters per level-2+ child (0..5; default
  *                       -1: 0 with hot tiles or the spread plan, else 4)
+ *   HM_TA_MIN           smallest final-aggregation work item in keys (a power
+ *                       of two in 1024..262144, else HM_E_ARG; default 16384)
+ *   HM_TA_ITEMS         the work item halves from 262144 keys, down to
+ *                       HM_TA_MIN, until the call holds this many items' worth
+ *                       of points (>= 1, else HM_E_ARG; default 128)
  * Returns the previous value in *old (if not NULL). */
 int hm_ctx_tune(hm_ctx* ctx, const char* name, double value, double* old);
 
@@ -227,7 +232,10 @@ int hm_last_error(hm_ctx* ctx, int64_t* index, int* kind);
  *       times the last run only)
  *   [6] hot tiles of the call (their points skipped levels 2..)
  *   [7] partition levels of the pipeline plan (0 if the call took the
- *       general path); 3 zooms per level for dense, evenly spread clouds */
+ *       general path); 3 zooms per level for dense, evenly spread clouds
+ *   [8] keys per final-aggregation work item of the last hm_count* pipeline
+ *       call (HM_TA_MIN, HM_TA_ITEMS; 0 if the call took the general path);
+ *       written only when n_stages > 8 */
 int hm_last_stats(hm_ctx* ctx, int64_t* slow_points, double* stage_us, int n_stages);
 
 /* Streaming: micro-batches folded into a heatmap resident in HBM (BASELINE

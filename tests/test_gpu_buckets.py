@@ -2,11 +2,14 @@
 
 The last pipeline level bins each zoom-(Z-7) bucket (128 x 128 zoom-Z tiles)
 by one of three kernels chosen by its key count: k_small_sort/k_small_emit
-(<= 2048 keys, one wavefront; register sorts of 64/128/256/512/1024/2048 keys),
-k_aggregate (dense, one 256K-key work item) and k_aggregate_merged (several
-items).  Every boundary is hit with several key patterns, and with zoom
-windows that drop some of the pyramid levels.  Expected counts: oracle.count_tiles
-(the per-zoom reduceByKey of heatmap.py:109-111 over tile ids).
+(<= HM_SP_MAX = 512 keys, one wavefront; register sorts of 64/128/256/512
+keys), k_aggregate (dense, one work item: 16384 keys at these call sizes, up
+to 262144 at the benchmark's) and k_aggregate_merged (several items).  Every
+boundary of the small path is hit with several key patterns, and with zoom
+windows that drop some of the pyramid levels; the sizes around a work item
+are in tests/test_gpu_agg_items.py, at every item size.  Expected counts:
+oracle.count_tiles (the per-zoom reduceByKey of heatmap.py:109-111 over tile
+ids).
 """
 import numpy as np
 import pytest

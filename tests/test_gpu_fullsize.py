@@ -63,6 +63,7 @@ def test_fullsize_cloud(gpu, name, hot):
         st = device.context(0).last_stats()[1]
     del lat, lon
     assert buf.nx == 0
+    assert int(st[8]) == 262144      # keys per aggregation item: the full HM_TA at these sizes
     if hot and name.startswith("skew"):
         assert int(st[6]) == 1
     if not hot:

@@ -151,6 +151,7 @@ def test_sparse_fallback_vs_oracle(gpu, n, zmin, zmax, fallback):
     lon[1::1000] = 200.0
     got = device.count(lat, lon, None, zmin, zmax)
     assert (int(got.stage_us[7]) == 0) == fallback   # slot 7: the plan's partition levels (0: general path)
+    assert int(got.stage_us[8]) == (0 if fallback else 16384)   # slot 8: keys per aggregation item (0: general path)
     _same(got.sorted(), oracle.count(lat, lon, None, zmin, zmax))
 
 

@@ -107,6 +107,7 @@ def test_hot_region_overflow_retry(gpu):
     with device.tuned(HM_HOT_MIN_KEYS=0):
         got = device.count(rows, cols, None, 0, Z, tiles=True)
     assert int(got.stage_us[6]) == 2
+    assert int(got.stage_us[8]) == 32768   # keys per aggregation item at 2^22 points (16384 below)
     _same(got, oracle.count_tiles(rows, cols, 0, Z))
 
 
@@ -126,6 +127,7 @@ def test_hot_three_tiles_48m(gpu):
     rows, cols = rows[perm], cols[perm]
     got = device.count(rows, cols, None, 0, Z, tiles=True)
     assert int(got.stage_us[6]) == 3
+    assert int(got.stage_us[8]) == 262144   # the full aggregation item (HM_TA) from 2^25 points
     ref = oracle.count_tiles(rows, cols, 0, Z)
     assert cells_digest(got.zoom, got.row, got.col, got.count) == \
         cells_digest(ref["zoom"], ref["row"], ref["col"], ref["count"])

@@ -88,6 +88,7 @@ def test_hot_children_many_runs(gpu, big_min):
     with device.tuned(**knobs):
         got = device.count(rows, cols, None, 0, Z, tiles=True)
     assert int(got.stage_us[6]) == 0
+    assert int(got.stage_us[8]) == 262144   # the full aggregation item (HM_TA) from 2^25 points
     ref = oracle.count_tiles(rows, cols, 0, Z)
     assert got.zoom.size == ref["zoom"].size
     assert cells_digest(got.zoom, got.row, got.col, got.count) == \
