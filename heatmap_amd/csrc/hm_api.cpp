@@ -3212,6 +3212,108 @@ extern "C" int hm_stream_expire(hm_stream* s, int64_t before_hour, int64_t* cell
     return HM_OK;
 }
 
+/* the whole log, compacted, in one pass (k_stream_export): the log's buckets
+ * are raw, so a cell's bucket key is its group and hour (no relabel, no merge) */
+extern "C" int hm_stream_export(hm_stream* s, uint64_t* keys_out, uint64_t* counts_out, uint32_t* groups_out,
+                                uint32_t* hours_out, int64_t capacity, int64_t* n_out)
+{
+    if (!s || !n_out || capacity < 0 || (capacity > 0 && (!keys_out || !counts_out))) return HM_E_ARG;
+    *n_out = 0;
+    HIPCHK(hipSetDevice(s->ctx->device));
+    int st;
+    if ((st = stream_compact(s))) return st;
+    *n_out = (int64_t)s->llen;
+    if (s->llen == 0) return HM_OK;
+    if ((int64_t)s->llen > capacity) return HM_E_CAPACITY;
+    HmsEmitArgs e;
+    e.keys = s->lkeys;
+    e.counts = s->lcounts;
+    e.n = s->llen;
+    e.buckets = s->bk;
+    e.cb = s->cb;
+    e.zmin = s->zmin;
+    e.zmax = s->zmax;
+    e.base = s->base;
+    e.keys_out = keys_out;
+    e.counts_out = counts_out;
+    e.groups_out = groups_out;
+    e.periods_out = hours_out;
+    hm_launch_stream_export(s->ctx->stream, e);
+    HIPCHK(hipGetLastError());
+    return HM_OK;
+}
+
+/* pre-aggregated cells appended at the log's tail (k_stream_import), their
+ * buckets listed as a batch's are; one state read-back, and the tail becomes
+ * part of the log only when every cell was valid and found a bucket */
+extern "C" int hm_stream_import(hm_stream* s, const uint64_t* keys, const uint64_t* counts, const uint32_t* groups,
+                                const uint32_t* hours, int64_t n, int flags)
+{
+    if (!s || n < 0 || (n > 0 && (!keys || !counts)) || (flags & ~HM_IMPORT_DISTINCT)) return HM_E_ARG;
+    hm_ctx* ctx = s->ctx;
+    ctx->last_err_index = -1;
+    ctx->last_err_kind = HM_OK;
+    if (n == 0) return HM_OK;
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t q = ctx->stream;
+    int st;
+    if ((st = stream_room(s, (uint64_t)n))) return st;
+    /* reset BFULL, EXOTIC, BMM, NLIST, ERR in one copy (as hm_stream_add) */
+    unsigned long long* init = s->hstate + HMS_ST_COUNT;
+    init[0] = init[1] = init[2] = init[3] = 0;
+    init[4] = ~0ull;
+    HIPCHK(hipMemcpyAsync(s->state + HMS_ST_BFULL, init, 5 * 8, hipMemcpyHostToDevice, q));
+    if (++s->epoch == 0) s->epoch = 1;
+    HmsImportArgs a;
+    a.keys = keys;
+    a.counts = counts;
+    a.groups = groups;
+    a.hours = hours;
+    a.n = (uint64_t)n;
+    a.buckets = s->bk;
+    a.cb = s->cb;
+    a.zmin = s->zmin;
+    a.zmax = s->zmax;
+    a.base = s->base;
+    a.keys_out = s->lkeys + s->llen;
+    a.counts_out = s->lcounts + s->llen;
+    a.bflag = s->bflag;
+    a.epoch = s->epoch;
+    a.state = s->state;
+    hm_launch_stream_import(q, a);
+    const uint64_t nb = s->bk.mask + 1;
+    hm_launch_stream_collect(q, s->bflag, nb, s->epoch, s->blist, s->state);
+    HIPCHK(hipGetLastError());
+    /* the import's bucket list comes back with the state: a first part is
+     * copied unasked (an export of a time-ordered stream has few buckets), the
+     * rest only when there is more */
+    std::vector<uint32_t> list((size_t)std::min<uint64_t>({(uint64_t)n, nb, 1024}));
+    HIPCHK(hipMemcpyAsync(list.data(), s->blist, list.size() * 4, hipMemcpyDeviceToHost, q));
+    if ((st = stream_sync_state(s))) return st;
+    const unsigned long long e = s->hstate[HMS_ST_ERR];
+    if (e != ~0ull) {
+        ctx->last_err_index = (int64_t)(e >> 8);
+        ctx->last_err_kind = HM_E_ARG;
+        return HM_E_ARG;
+    }
+    if (s->hstate[HMS_ST_BFULL]) return HM_E_CAPACITY;   /* max_buckets (group, hour) pairs */
+    const uint64_t nlist = s->hstate[HMS_ST_NLIST];
+    if (nlist > nb) return HM_E_HIP;   /* cannot happen */
+    if (nlist > list.size()) {
+        list.resize((size_t)nlist);
+        HIPCHK(hipMemcpyAsync(list.data(), s->blist, (size_t)nlist * 4, hipMemcpyDeviceToHost, q));
+        HIPCHK(hm_sync(q));
+    }
+    /* compactness: the log's buckets stay exactly known (the import's list
+     * joins them); its keys stay distinct only when the caller promises the
+     * input's are and none of its buckets has cells in the log yet */
+    if (s->llen == 0) s->compact = true;
+    stream_appended(s, (uint64_t)n, list.data(), (uint32_t)nlist);
+    if (!(flags & HM_IMPORT_DISTINCT)) s->compact = false;
+    s->last_nparts = 1;   /* the next batch is counted speculatively as one bucket again */
+    return HM_OK;
+}
+
 extern "C" int hm_stream_extract(hm_stream* s, int64_t hour, uint64_t* keys_out, uint64_t* counts_out,
                                  uint32_t* hours_out, int64_t capacity, int64_t* n_out)
 {

@@ -648,6 +648,23 @@ struct HmsEmitArgs {
     uint32_t* groups_out;
     uint32_t* periods_out;
 };
+/* pre-aggregated cells appended at the log's tail (k_stream_import) */
+struct HmsImportArgs {
+    const uint64_t* keys;    /* hm_count layout */
+    const uint64_t* counts;
+    const uint32_t* groups;  /* NULL: HMS_NOGROUP */
+    const uint32_t* hours;   /* epoch hours or HM_STREAM_UNDATED; NULL: every cell undated */
+    uint64_t n;
+    HmsBuckets buckets;
+    int cb, zmin, zmax;
+    uint32_t base;
+    uint64_t* keys_out;      /* the log's tail: bucket << cb | cell, cell i at [i] */
+    uint64_t* counts_out;
+    uint32_t* bflag;         /* per bucket: epoch of the last batch that met it */
+    uint32_t epoch;          /* this import's (nonzero) */
+    unsigned long long* state;    /* HMS_ST_BUCKETS, HMS_ST_BFULL, HMS_ST_ERR (first bad cell << 8 | HM_E_ARG) */
+};
+void hm_launch_stream_import(hipStream_t s, const HmsImportArgs& a);
 void hm_launch_stream_buckets(hipStream_t s, const HmsBucketArgs& a);
 void hm_launch_stream_batch_list(hipStream_t s, const uint32_t* list, uint32_t nlist, uint32_t* loc);
 void hm_launch_stream_collect(hipStream_t s, const uint32_t* bflag, uint64_t nb, uint32_t epoch, uint32_t* list,
@@ -666,6 +683,8 @@ void hm_launch_stream_init(hipStream_t s, const HmsTable& t);
 void hm_launch_stream_fill(hipStream_t s, uint64_t* p, uint64_t n, uint64_t v);
 void hm_launch_stream_relabel(hipStream_t s, const HmsRelabelArgs& a);
 void hm_launch_stream_emit(hipStream_t s, const HmsEmitArgs& a);
+/* the log itself -> caller's arrays: periods_out receives epoch hours or HM_STREAM_UNDATED (k_stream_export) */
+void hm_launch_stream_export(hipStream_t s, const HmsEmitArgs& a);
 void hm_launch_stream_view(hipStream_t s, const HmsViewArgs& a);
 void hm_launch_stream_expire(hipStream_t s, const HmsExpireArgs& a);
 /* the occupied slots of a bucket table -> list, their number added to *n */

@@ -32,7 +32,10 @@
  * Retention (hm_stream_expire, k_stream_expire)
  * filters the log into the alternate arrays and moves the surviving buckets
  * to a fresh bucket table, which frees the slots of the expired hours and of
- * every rollup label.
+ * every rollup label.  The state leaves and enters as cells: hm_stream_export
+ * lists the compacted log with each cell's group and hour (k_stream_export,
+ * one pass), hm_stream_import appends such cells at the tail under interned
+ * buckets (k_stream_import: a snapshot restored, another stream merged in).
  */
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -465,6 +468,51 @@ __global__ __launch_bounds__(256) void k_stream_emit(HmsEmitArgs a)
     }
 }
 
+/* pyramid cell index -> hm_count key without the zoom search: the zoom is the
+ * largest z with off(z) = (4^z - 1)/3 <= id, that is 4^z <= 3 id + 1 */
+__device__ __forceinline__ uint64_t hms_cell_key_log(uint64_t id, int zmin, int zmax)
+{
+    const int z = min(max((63 - __clzll((long long)(3ull * id + 1ull))) >> 1, zmin), zmax);
+    const uint64_t m = id - hms_pyr_off(z);
+    return ((uint64_t)z << 58) | ((m >> z) << 29) | (m & ((1ull << z) - 1ull));
+}
+
+/* The export's one pass (hm_stream_export), over the log itself: its buckets
+ * are raw, so a cell's bucket key is its group and its hour (periods_out: the
+ * epoch hour, or HM_STREAM_UNDATED for an undated bucket).  A block takes
+ * 256 * HMS_XP_U cells at a time; a thread issues the loads of its HMS_XP_U
+ * keys and counts together, then the bucket-key lookups (two dependent loads
+ * per cell, as k_stream_expire). */
+#define HMS_XP_U 8
+__global__ __launch_bounds__(256) void k_stream_export(HmsEmitArgs a)
+{
+    constexpr int U = HMS_XP_U;
+    const int tid = threadIdx.x;
+    const uint64_t cmask = (1ull << a.cb) - 1ull;
+    constexpr uint64_t CH = 256 * U;
+    for (uint64_t c0 = (uint64_t)blockIdx.x * CH; c0 < a.n; c0 += (uint64_t)gridDim.x * CH) {
+        uint64_t k[U], cn[U], bk[U];
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const uint64_t i = c0 + (uint64_t)u * 256 + tid;
+            k[u] = i < a.n ? a.keys[i] : 0ull;
+            cn[u] = i < a.n ? a.counts[i] : 0ull;
+        }
+#pragma unroll
+        for (int u = 0; u < U; u++) bk[u] = a.buckets.keys[(k[u] >> a.cb) & a.buckets.mask];
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const uint64_t i = c0 + (uint64_t)u * 256 + tid;
+            if (i >= a.n) continue;
+            const uint32_t pw = (uint32_t)bk[u];
+            a.keys_out[i] = hms_cell_key_log(k[u] & cmask, a.zmin, a.zmax);
+            a.counts_out[i] = cn[u];
+            if (a.groups_out) a.groups_out[i] = (uint32_t)(bk[u] >> 32);
+            if (a.periods_out) a.periods_out[i] = pw == HMS_UNDATED ? HM_STREAM_UNDATED : a.base + pw;
+        }
+    }
+}
+
 /* label key of a raw bucket key in a view (the window's or alltime's label,
  * under the group, HMS_ALLGROUPS or the selected group), or ~0: not in it */
 __device__ __forceinline__ uint64_t hms_view_key(const HmsViewArgs& a, uint64_t bk)
@@ -681,6 +729,94 @@ __global__ __launch_bounds__(256) void k_stream_expire(HmsExpireArgs a)
     }
 }
 
+/* Import of pre-aggregated cells (hm_stream_import): cell i of the input goes
+ * to the log's tail at position i under the bucket of its (group, hour), so
+ * the stores are as coalesced as the loads and nothing is reserved.  A block
+ * takes 256 * HMS_IM_U cells at a time (k_stream_expire's shape); a thread
+ * issues the loads of its HMS_IM_U keys, groups and hours together, then the
+ * counts.  Interning as k_stream_expire: the lanes sharing lane 0's (group,
+ * hour) intern it once and the wave remembers it (an export of a time-ordered
+ * stream is long runs of one bucket: no probe at all), the others probe alone.
+ * Every bucket met is flagged with the import's epoch (k_stream_collect lists
+ * them afterwards).  An invalid cell (zoom outside the stream's, row or col
+ * outside the square, count 0, group 0xFFFFFFFF, hour outside the stream's) is
+ * not written; the first one's index goes to HMS_ST_ERR and the caller drops
+ * the tail. */
+#define HMS_IM_U 8
+__global__ __launch_bounds__(256) void k_stream_import(HmsImportArgs a)
+{
+    constexpr int U = HMS_IM_U;
+    __shared__ unsigned long long sbad[256 / 64];
+    const int tid = threadIdx.x;
+    uint32_t bclaimed = 0, full = 0;
+    uint64_t bad = ~0ull;             /* the first invalid cell this thread met */
+    uint64_t wk = HMS_EMPTY;          /* the wave's last shared key and its bucket */
+    uint32_t wb = HMS_NO_BUCKET;
+    constexpr uint64_t CH = 256 * U;
+    for (uint64_t c0 = (uint64_t)blockIdx.x * CH; c0 < a.n; c0 += (uint64_t)gridDim.x * CH) {
+        uint64_t k[U], cn[U];
+        uint32_t g[U], h[U];
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const uint64_t i = c0 + (uint64_t)u * 256 + tid;
+            k[u] = i < a.n ? a.keys[i] : 0ull;
+            g[u] = (a.groups && i < a.n) ? a.groups[i] : HMS_NOGROUP;
+            h[u] = (a.hours && i < a.n) ? a.hours[i] : HM_STREAM_UNDATED;
+        }
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const uint64_t i = c0 + (uint64_t)u * 256 + tid;
+            cn[u] = i < a.n ? a.counts[i] : 0ull;
+        }
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const uint64_t i = c0 + (uint64_t)u * 256 + tid;
+            const int z = (int)(k[u] >> 58);
+            const uint64_t r = (k[u] >> 29) & 0x1FFFFFFFull, c = k[u] & 0x1FFFFFFFull;
+            const bool dated = h[u] != HM_STREAM_UNDATED;
+            const bool ok = i < a.n && z >= a.zmin && z <= a.zmax && (r >> z) == 0 && (c >> z) == 0 && cn[u] != 0 &&
+                            g[u] != HMS_ALLGROUPS &&
+                            (!dated || (h[u] >= a.base && h[u] - a.base < HMS_MAX_HOUR_OFFSET));
+            if (i < a.n && !ok) bad = min(bad, i);
+            const uint64_t bk = ok ? ((uint64_t)g[u] << 32) | (dated ? h[u] - a.base : HMS_UNDATED) : ~0ull;
+            const uint64_t k0 = ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(bk >> 32)) << 32) |
+                                __builtin_amdgcn_readfirstlane((uint32_t)bk);
+            const bool same = ok & (bk == k0);
+            const uint64_t sm = __ballot(same);
+            if (sm && k0 != wk) {
+                uint32_t b0 = 0;
+                if (hm_lane() == 0) {   /* lane 0 is in the group */
+                    b0 = hms_intern(a.buckets, k0, &bclaimed);
+                    if (b0 != HMS_NO_BUCKET && a.bflag[b0] != a.epoch) a.bflag[b0] = a.epoch;
+                }
+                wb = __shfl(b0, 0, 64);
+                wk = k0;
+            }
+            uint32_t b = wb;
+            if (ok && !same) {
+                b = hms_intern(a.buckets, bk, &bclaimed);
+                if (b != HMS_NO_BUCKET && a.bflag[b] != a.epoch) a.bflag[b] = a.epoch;
+            }
+            if (ok) {
+                full |= b == HMS_NO_BUCKET;   /* the caller drops the tail */
+                a.keys_out[i] = ((uint64_t)(b == HMS_NO_BUCKET ? 0u : b) << a.cb) | hms_cell(k[u]);
+                a.counts_out[i] = cn[u];
+            }
+        }
+    }
+    uint64_t v[2] = {bclaimed, full};
+    hms_block_sums(v);
+    for (int o = 32; o > 0; o >>= 1) bad = min(bad, (uint64_t)__shfl_xor((unsigned long long)bad, o, 64));
+    if ((tid & 63) == 0) sbad[tid >> 6] = bad;
+    __syncthreads();
+    if (tid == 0) {
+        if (v[0]) atomicAdd(&a.state[HMS_ST_BUCKETS], (unsigned long long)v[0]);
+        if (v[1]) atomicAdd(&a.state[HMS_ST_BFULL], (unsigned long long)v[1]);
+        const unsigned long long m = min(min(sbad[0], sbad[1]), min(sbad[2], sbad[3]));
+        if (m != ~0ull) atomicMin(&a.state[HMS_ST_ERR], (m << 8) | (unsigned long long)HM_E_ARG);
+    }
+}
+
 /* the occupied slots of a bucket table, listed (one atomic per wave that
  * finds any) */
 __global__ __launch_bounds__(256) void k_stream_occupied(HmsBuckets b, uint32_t* __restrict__ list,
@@ -801,6 +937,12 @@ void hm_launch_stream_emit(hipStream_t s, const HmsEmitArgs& a)
     if (a.n) hipLaunchKernelGGL(k_stream_emit, hms_grid(a.n), dim3(256), 0, s, a);
 }
 
+void hm_launch_stream_export(hipStream_t s, const HmsEmitArgs& a)
+{
+    const uint64_t chunks = (a.n + 256 * HMS_XP_U - 1) / (256 * HMS_XP_U);
+    if (a.n) hipLaunchKernelGGL(k_stream_export, dim3((unsigned)(chunks < 2048 ? chunks : 2048)), dim3(256), 0, s, a);
+}
+
 void hm_launch_stream_view(hipStream_t s, const HmsViewArgs& a)
 {
     const uint64_t chunks = (a.n + 256 * HMS_VW_U - 1) / (256 * HMS_VW_U);
@@ -811,6 +953,12 @@ void hm_launch_stream_expire(hipStream_t s, const HmsExpireArgs& a)
 {
     const uint64_t chunks = (a.n + 256 * HMS_RL_PPT - 1) / (256 * HMS_RL_PPT);
     if (a.n) hipLaunchKernelGGL(k_stream_expire, dim3((unsigned)(chunks < 1024 ? chunks : 1024)), dim3(256), 0, s, a);
+}
+
+void hm_launch_stream_import(hipStream_t s, const HmsImportArgs& a)
+{
+    const uint64_t chunks = (a.n + 256 * HMS_IM_U - 1) / (256 * HMS_IM_U);
+    if (a.n) hipLaunchKernelGGL(k_stream_import, dim3((unsigned)(chunks < 2048 ? chunks : 2048)), dim3(256), 0, s, a);
 }
 
 void hm_launch_stream_occupied(hipStream_t s, const HmsBuckets& b, uint32_t* list, unsigned long long* n)

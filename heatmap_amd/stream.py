@@ -22,6 +22,12 @@ label is a device rollup of the hour buckets:
                                pass over the log's keys)
   expire(before_hour)          retention: the cells of hours < before_hour
                                leave the stream, their buckets are freed
+  snapshot() / save(path)      the whole state as arrays (hm_stream_export: one
+                               record per (group, hour, cell)), and back:
+                               load(path), from_snapshot(), restore()
+  import_cells(...)            pre-aggregated cells appended (hm_stream_import)
+  merge_from(other)            another stream's cells added, groups matched by
+                               label: shards of one feed, or a backfill
   rows(timespan)               build_heatmaps' rows, {id: {bin: count}}, for
                                'alltime', 'year', 'month' or 'day' (UTC dates
                                of the epoch hours), with the reference's user
@@ -143,6 +149,102 @@ def _expire_records(x: np.ndarray, before_hour: int):
     h = x[:, 1]
     gone = (h != UNDATED_HOUR) & (h < before_hour)
     return x[~gone], int(gone.sum())
+
+
+SNAPSHOT_VERSION = 1      # format of snapshot() / save()
+_SNAPSHOT_KEYS = ("version", "zmin", "zmax", "base_hour", "labels", "explicit_max", "keys", "counts", "groups",
+                  "hours", "x")
+
+
+def _group_lut(src_labels, index: dict, labels: list) -> np.ndarray:
+    """int64 LUT from another stream's group ids (src_labels: its id -> label
+    list) to this stream's (index: label -> id, labels: id -> label; labels
+    it does not know yet are appended to both).  One more entry than
+    src_labels: the last one maps NOGROUP to itself (_remap_groups)."""
+    lut = np.empty(len(src_labels) + 1, dtype=np.int64)
+    for j, label in enumerate(src_labels):
+        label = str(label)
+        if label not in index:
+            index[label] = len(labels)
+            labels.append(label)
+        lut[j] = index[label]
+    lut[-1] = NOGROUP
+    return lut
+
+
+def _remap_groups(g, lut):
+    """Group ids g (int64, a numpy array or a torch tensor) through a
+    _group_lut of the same kind: one gather.  NOGROUP passes through; any other
+    id without a label is a ValueError naming the first such cell."""
+    n = len(lut) - 1
+    bad = (g >= n) & (g != NOGROUP)
+    if bool(bad.any()):
+        i = int(np.flatnonzero(bad)[0]) if isinstance(bad, np.ndarray) else int(bad.nonzero()[0, 0])
+        raise ValueError("cell %d: group id %d has no label (the source has %d)" % (i, int(g[i]), n))
+    return lut[g.clip(max=n)]
+
+
+def _explicit_group_max(g) -> int:
+    """Largest of the explicit group ids g (int64, numpy or torch) that name a
+    group, -1 for none: NOGROUP is a cell without one, and 0xFFFFFFFF is left
+    to hm_stream_import, which reports the first invalid cell of any kind."""
+    named = g[g < NOGROUP]
+    return int(named.max()) if len(named) else -1
+
+
+def _remap_records(x: np.ndarray, lut: np.ndarray) -> np.ndarray:
+    """Out-of-square records x (group, hour, zoom, row, col, count) of another
+    stream under this stream's group ids."""
+    x = np.array(x, dtype=np.int64).reshape(-1, 6)
+    if len(x):
+        x[:, 0] = _remap_groups(x[:, 0], lut)
+    return x
+
+
+def _pack_snapshot(zmin, zmax, base_hour, labels, explicit_max, keys, counts, groups, hours, x) -> dict:
+    """A stream's state as numpy arrays and plain numbers (snapshot())."""
+    return {"version": SNAPSHOT_VERSION, "zmin": int(zmin), "zmax": int(zmax), "base_hour": int(base_hour),
+            "labels": np.array([str(v) for v in labels], dtype=np.str_), "explicit_max": int(explicit_max),
+            "keys": np.ascontiguousarray(keys, dtype=np.uint64), "counts": np.ascontiguousarray(counts, dtype=np.uint64),
+            "groups": np.ascontiguousarray(groups, dtype=np.uint32), "hours": np.ascontiguousarray(hours, dtype=np.uint32),
+            "x": np.ascontiguousarray(x, dtype=np.int64).reshape(-1, 6)}
+
+
+def _unpack_snapshot(snap) -> dict:
+    """A snapshot dict or an opened .npz checked and brought to the types
+    _pack_snapshot writes; an unknown format version is refused."""
+    missing = [k for k in _SNAPSHOT_KEYS if k not in snap]
+    if "version" in missing:
+        raise ValueError("not a StreamingHeatmap snapshot (no format version)")
+    version = int(np.asarray(snap["version"]))
+    if version != SNAPSHOT_VERSION:
+        raise ValueError("snapshot format version %d is not supported (this package reads version %d)"
+                         % (version, SNAPSHOT_VERSION))
+    if missing:
+        raise ValueError("snapshot lacks %s" % ", ".join(missing))
+    out = _pack_snapshot(*(np.asarray(snap[k]) for k in _SNAPSHOT_KEYS[1:4]), np.asarray(snap["labels"]).tolist(),
+                         np.asarray(snap["explicit_max"]), snap["keys"], snap["counts"], snap["groups"], snap["hours"],
+                         snap["x"])
+    n = len(out["keys"])
+    if any(len(out[k]) != n for k in ("counts", "groups", "hours")):
+        raise ValueError("snapshot arrays differ in length")
+    return out
+
+
+def _save_snapshot(path, snap: dict):
+    """np.savez of a snapshot: arrays only, nothing pickled."""
+    np.savez(path, **{k: np.asarray(v) for k, v in snap.items()})
+
+
+def _load_snapshot(path) -> dict:
+    with np.load(path, allow_pickle=False) as f:
+        return _unpack_snapshot(f)
+
+
+def _check_zooms(snap: dict, zmin: int, zmax: int):
+    if (snap["zmin"], snap["zmax"]) != (zmin, zmax):
+        raise ValueError("snapshot holds zooms %d..%d, the stream %d..%d"
+                         % (snap["zmin"], snap["zmax"], zmin, zmax))
 
 
 def span_label(timespan: str, period: int) -> str:
@@ -612,6 +714,224 @@ class StreamingHeatmap:
             _lib.raise_for(rc)
         self._x, gone = _expire_records(self._x, int(before_hour))
         return a.value + gone, b.value
+
+    # ------------------------------------------------- snapshots and merging
+
+    def export_device(self):
+        """(n, keys, counts, groups, hours) as torch CUDA tensors: the whole
+        resident state, one record per distinct (group, hour, cell)
+        (hm_stream_export: hm_count key layout, group NOGROUP for none, hour
+        HM_STREAM_UNDATED's bits for an undated cell; out-of-square cells not
+        included)."""
+        torch = self._torch
+        self.ctx.bind_stream()
+        cap = max(1, self.cells()[0])      # exact: the export compacts the log as cells() does
+        dev = "cuda:%d" % self.device_index
+        while True:
+            keys = torch.empty(cap, dtype=torch.int64, device=dev)
+            counts = torch.empty(cap, dtype=torch.int64, device=dev)
+            groups = torch.empty(cap, dtype=torch.int32, device=dev)
+            hours = torch.empty(cap, dtype=torch.int32, device=dev)
+            n = ctypes.c_int64(0)
+            rc = self.ctx.L.hm_stream_export(self.ptr, device._ptr(keys), device._ptr(counts), device._ptr(groups),
+                                             device._ptr(hours), cap, ctypes.byref(n))
+            if rc == _lib.HM_E_CAPACITY and n.value > cap:
+                cap = n.value + 1024
+                continue
+            if rc != _lib.HM_OK:
+                _lib.raise_for(rc)
+            return n.value, keys, counts, groups, hours
+
+    def export(self):
+        """Host arrays (group u32, hour int64, zoom, row, col, count) of every
+        record held, hour UNDATED_HOUR (-1) for undated cells, cells outside
+        the square included."""
+        n, keys, counts, groups, hours = self.export_device()
+        z, r, c = device.decode_keys(keys[:n].cpu().numpy().view(np.uint64))
+        h = hours[:n].cpu().numpy().view(np.uint32).astype(np.int64)
+        h[h == _lib.HM_STREAM_UNDATED] = UNDATED_HOUR
+        out = (groups[:n].cpu().numpy().view(np.uint32), h, z, r, c, counts[:n].cpu().numpy())
+        if not len(self._x):
+            return out
+        return tuple(np.concatenate([a, self._x[:, j].astype(a.dtype)]) for j, a in enumerate(out))
+
+    def _cells_u32(self, x, n, what, undated=False):
+        """uint32 values per cell as an int32 device tensor (their bits).
+        Signed 64-bit input is range-checked (UNDATED_HOUR -> HM_STREAM_UNDATED
+        for hours); int32 / uint32 input is taken as bits."""
+        torch = self._torch
+        if x is None:
+            return None
+        if not isinstance(x, torch.Tensor):
+            a = np.asarray(x)
+            if a.dtype.kind not in "iu":
+                raise TypeError("%s must be integers" % what)
+            if a.dtype.itemsize == 4:
+                x = torch.from_numpy(np.ascontiguousarray(a).view(np.int32))
+            else:
+                x = torch.from_numpy(np.ascontiguousarray(a.astype(np.int64)))
+        elif getattr(torch, "uint32", None) is not None and x.dtype == torch.uint32:
+            x = x.view(torch.int32)
+        if x.numel() != n:
+            raise ValueError("%s must have one entry per cell" % what)
+        if x.dtype != torch.int32:
+            x = device._dev(x, torch.int64, self.device_index)
+            if undated:
+                x = torch.where(x == UNDATED_HOUR, torch.full_like(x, _lib.HM_STREAM_UNDATED), x)
+            bad = (x < 0) | (x > 0xFFFFFFFF)
+            if bool(bad.any()):
+                raise ValueError("cell %d: %s does not fit 32 bits" % (int(bad.nonzero()[0, 0]), what))
+            # the low 32 bits, as int32
+            x = torch.where(x >= (1 << 31), x - (1 << 32), x)
+        return device._dev(x, torch.int32, self.device_index)
+
+    def import_cells(self, keys, counts, groups=None, hours=None, labels=None, distinct=False):
+        """Append pre-aggregated cells (hm_stream_import): keys in hm_count's
+        layout and their counts, numpy arrays or CUDA tensors.  groups: uint32
+        group ids (None: no cell has a group), hours: epoch hours, UNDATED_HOUR
+        or HM_STREAM_UNDATED for an undated cell (None: all undated).  labels:
+        the source stream's id -> label list; the ids are then remapped to this
+        stream's (unknown labels are appended, NOGROUP passes through).
+        Without labels the ids are explicit, as add(group=)'s.  distinct: no
+        two cells share (group, hour, key), as an export's.  Equal cells add
+        up, in the input and with the stream's.  An invalid cell raises
+        ValueError naming the first one's index; nothing is appended then."""
+        torch = self._torch
+        self.ctx.bind_stream()
+
+        def u64(x):
+            if not isinstance(x, torch.Tensor):
+                a = np.asarray(x)
+                if a.dtype.kind not in "iu" or a.dtype.itemsize != 8:
+                    a = a.astype(np.uint64)
+                x = torch.from_numpy(np.ascontiguousarray(a).view(np.int64))
+            elif getattr(torch, "uint64", None) is not None and x.dtype == torch.uint64:
+                x = x.view(torch.int64)
+            return device._dev(x, torch.int64, self.device_index)
+
+        k, cn = u64(keys), u64(counts)
+        n = k.numel()
+        if cn.numel() != n:
+            raise ValueError("keys and counts must have the same length")
+        gr = self._cells_u32(groups, n, "group")
+        hr = self._cells_u32(hours, n, "hour", undated=True)
+        index, new_labels, explicit_max = self._index, self.labels, self._explicit_max
+        if gr is not None:
+            g64 = gr.to(torch.int64) & 0xFFFFFFFF
+            if labels is not None:
+                index, new_labels = dict(self._index), list(self.labels)    # committed when the import succeeds
+                lut = torch.from_numpy(_group_lut(labels, index, new_labels)).to(g64.device)
+                g64 = _remap_groups(g64, lut)
+                gr = torch.where(g64 >= (1 << 31), g64 - (1 << 32), g64).to(torch.int32)
+            else:
+                explicit_max = max(explicit_max, _explicit_group_max(g64))
+        rc = self.ctx.L.hm_stream_import(self.ptr, device._ptr(k), device._ptr(cn), device._ptr(gr), device._ptr(hr),
+                                         n, _lib.HM_IMPORT_DISTINCT if distinct else 0)
+        if rc == _lib.HM_E_ARG:
+            idx, _ = self.ctx.last_error()
+            raise ValueError("cell %d is not a valid cell of this stream (zooms %d..%d, row and col inside the "
+                             "square, count >= 1, group <= 0x%X, hour undated or in [%d, %d))"
+                             % (idx, self.zmin, self.zmax, NOGROUP, self.base_hour, self.base_hour + MAX_HOURS))
+        if rc != _lib.HM_OK:
+            _lib.raise_for(rc)
+        self._index, self.labels, self._explicit_max = index, new_labels, explicit_max
+
+    def snapshot(self) -> dict:
+        """The stream's whole state as numpy arrays and plain numbers: format
+        version, zmin, zmax, base_hour, the group labels, the largest explicit
+        group id, the export (keys, counts, groups, hours as hm_stream_export
+        writes them) and the out-of-square records."""
+        n, keys, counts, groups, hours = self.export_device()
+        return _pack_snapshot(self.zmin, self.zmax, self.base_hour, self.labels, self._explicit_max,
+                              keys[:n].cpu().numpy().view(np.uint64), counts[:n].cpu().numpy().view(np.uint64),
+                              groups[:n].cpu().numpy().view(np.uint32), hours[:n].cpu().numpy().view(np.uint32),
+                              self._x)
+
+    def save(self, path):
+        """Write snapshot() to `path` (numpy's .npz; no pickled objects)."""
+        with open(path, "wb") as f:
+            _save_snapshot(f, self.snapshot())
+
+    def _take(self, labels, explicit_max, x, keys, counts, groups, hours, distinct):
+        """Another stream's cells (device tensors or host arrays), labels and
+        out-of-square records x joined into this one."""
+        labels = [str(v) for v in labels]
+        if int(explicit_max) >= len(labels):
+            # ids passed as group= have no label to remap by: they keep their
+            # values, which needs the labelled ids to mean the same here
+            m = min(len(labels), len(self.labels))
+            if labels[:m] != self.labels[:m]:
+                raise ValueError("the source holds explicit group ids (up to %d) and its labels %r do not line up "
+                                 "with this stream's %r" % (int(explicit_max), labels, self.labels))
+            self.import_cells(keys, counts, groups, hours, None, distinct)
+            lut = _group_lut(labels, self._index, self.labels)
+            lut = np.concatenate([lut[:-1], np.arange(len(labels), int(explicit_max) + 1), lut[-1:]])
+        else:
+            self.import_cells(keys, counts, groups, hours, labels, distinct)
+            lut = _group_lut(labels, self._index, self.labels)      # (all known by now)
+        self._explicit_max = max(self._explicit_max, int(explicit_max))
+        if len(x):
+            self._x = _sum_records(np.concatenate([self._x, _remap_records(x, lut)]), 5)
+
+    def _check_hours(self, lo, hi, what):
+        """ValueError unless the dated hours lo..hi (None: none) fit this stream"""
+        if lo is not None and (lo < self.base_hour or hi >= self.base_hour + MAX_HOURS):
+            raise ValueError("%s holds hours %d..%d, outside this stream's [%d, %d)"
+                             % (what, lo, hi, self.base_hour, self.base_hour + MAX_HOURS))
+
+    def restore(self, snapshot):
+        """Join a snapshot() (or an opened .npz of one) into this stream: its
+        zooms must be this stream's and its hours must fit; into a fresh
+        stream this restores the snapshot's state."""
+        snap = _unpack_snapshot(snapshot)
+        _check_zooms(snap, self.zmin, self.zmax)
+        h = np.concatenate([snap["hours"][snap["hours"] != _lib.HM_STREAM_UNDATED].astype(np.int64),
+                            snap["x"][snap["x"][:, 1] != UNDATED_HOUR, 1]])
+        self._check_hours(int(h.min()) if len(h) else None, int(h.max()) if len(h) else None, "the snapshot")
+        self._take(snap["labels"].tolist(), snap["explicit_max"], snap["x"], snap["keys"], snap["counts"],
+                   snap["groups"], snap["hours"], True)
+        return self
+
+    @classmethod
+    def from_snapshot(cls, snapshot, **create_kwargs):
+        """A new stream holding the snapshot's state (zooms and base hour from
+        the snapshot unless given; other create_kwargs as the constructor's)."""
+        snap = _unpack_snapshot(snapshot)
+        kw = dict(zmin=snap["zmin"], zmax=snap["zmax"], base_hour=snap["base_hour"],
+                  initial_cells=max(1 << 20, len(snap["keys"]) + len(snap["keys"]) // 4))
+        kw.update(create_kwargs)
+        _check_zooms(snap, int(kw["zmin"]), int(kw["zmax"]))
+        s = cls(**kw)
+        try:
+            return s.restore(snap)
+        except Exception:
+            s.close()
+            raise
+
+    @classmethod
+    def load(cls, path, **create_kwargs):
+        """A new stream from a file written by save()."""
+        return cls.from_snapshot(_load_snapshot(path), **create_kwargs)
+
+    def merge_from(self, other: "StreamingHeatmap"):
+        """Add every cell of `other` (same zooms; its base hour may differ, its
+        hours must fit this stream's) to this stream: shards of one feed, or a
+        backfill.  Groups are matched by label.  `other` is left unchanged;
+        nothing changes here when its hours do not fit."""
+        torch = self._torch
+        if (other.zmin, other.zmax) != (self.zmin, self.zmax):
+            raise ValueError("merge_from needs equal zooms: %d..%d against %d..%d"
+                             % (other.zmin, other.zmax, self.zmin, self.zmax))
+        n, keys, counts, groups, hours = other.export_device()
+        h = hours[:n].to(torch.int64) & 0xFFFFFFFF
+        h = h[h != _lib.HM_STREAM_UNDATED]
+        xh = other._x[other._x[:, 1] != UNDATED_HOUR, 1]
+        ends = ([int(h.min()), int(h.max())] if h.numel() else []) + ([int(xh.min()), int(xh.max())] if len(xh) else [])
+        self._check_hours(min(ends, default=None), max(ends, default=None), "the other stream")
+        dev = "cuda:%d" % self.device_index
+        self.ctx.bind_stream()
+        self._take(list(other.labels), other._explicit_max, other._x, keys[:n].to(dev), counts[:n].to(dev),
+                   groups[:n].to(dev), hours[:n].to(dev), True)
 
     def hourly(self):
         """{epoch hour: Counts} for every non-empty hour."""

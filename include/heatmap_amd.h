@@ -303,7 +303,36 @@ int hm_last_stats(hm_ctx* ctx, int64_t* slow_points, double* stage_us, int n_sta
  *                     again (either may be NULL).  before_hour <= base_hour, or
  *                     a cut below which the log holds nothing, changes nothing
  *                     and gives (0, 0).  A later batch may bring an expired hour
- *                     back.  Enqueued after all pending work; waits once. */
+ *                     back.  Enqueued after all pending work; waits once.
+ *   hm_stream_export  the stream's whole state: one record per distinct
+ *                     (group, hour or undated, cell), the log compacted and
+ *                     listed in one pass (no rollup).  Keys in hm_count's
+ *                     layout; groups as hm_stream_rollup's (0xFFFFFFFE: no
+ *                     group); hours_out receives the epoch hour, or
+ *                     HM_STREAM_UNDATED for a cell added without one.
+ *                     groups_out/hours_out may be NULL.  Unspecified order;
+ *                     HM_E_CAPACITY and *n_out as hm_stream_rollup; an empty
+ *                     stream is HM_OK with *n_out = 0.  The log is left as it
+ *                     is, apart from being compact.
+ *   hm_stream_import  appends n pre-aggregated cells (device arrays, as
+ *                     hm_stream_export writes them): a snapshot restored, another
+ *                     stream's or shard's cells, a backfill counted with
+ *                     hm_count.  groups NULL: no cell has a group; hours NULL:
+ *                     every cell is undated.  Equal (group, hour, key) may repeat
+ *                     in the input and against the stream: their counts add, as
+ *                     two batches of one hour do.  flags: HM_IMPORT_DISTINCT
+ *                     promises that no two input cells share (group, hour, key)
+ *                     (an export is such): the stream then need not merge its
+ *                     log before the next exact size is asked for; a false
+ *                     promise only lets hm_stream_cells over-count.  A cell is
+ *                     valid when zmin <= zoom <= zmax, row and col < 2^zoom,
+ *                     count >= 1, group <= 0xFFFFFFFE and hour is
+ *                     HM_STREAM_UNDATED or in [base_hour, base_hour + 2^28): any
+ *                     other gives HM_E_ARG, hm_last_error() the index of the
+ *                     first one (input order), and nothing is appended.
+ *                     HM_E_CAPACITY: no bucket left (max_buckets), nothing is
+ *                     appended.  A failing import may leave unused buckets
+ *                     behind, never cells.  n = 0 is HM_OK.  Waits once. */
 #define HM_STREAM_ALLTIME (-1)
 #define HM_STREAM_EACH_HOUR (-2)
 #define HM_STREAM_MAX_HOURS (1 << 28)
@@ -333,6 +362,12 @@ int hm_stream_window(hm_stream* s, int64_t hour_lo, int64_t hour_hi, int merge_g
 int hm_stream_view(hm_stream* s, int64_t hour_lo, int64_t hour_hi, int64_t group, const int64_t* rects, int nrects,
                    uint64_t* keys_out, uint64_t* counts_out, uint32_t* groups_out, int64_t capacity, int64_t* n_out);
 int hm_stream_expire(hm_stream* s, int64_t before_hour, int64_t* cells_dropped, int64_t* buckets_freed);
+#define HM_STREAM_UNDATED 0xFFFFFFFFu   /* hours[]: a cell without an hour */
+#define HM_IMPORT_DISTINCT 1            /* flags: no two input cells share (group, hour, key) */
+int hm_stream_export(hm_stream* s, uint64_t* keys_out, uint64_t* counts_out, uint32_t* groups_out,
+                     uint32_t* hours_out, int64_t capacity, int64_t* n_out);
+int hm_stream_import(hm_stream* s, const uint64_t* keys, const uint64_t* counts, const uint32_t* groups,
+                     const uint32_t* hours, int64_t n, int flags);
 int hm_stream_destroy(hm_stream* s);
 
 /* Multi-GPU exchange of hm_count cells (one process per GPU; the collectives

@@ -36,6 +36,22 @@ the window's filtered by rectangle on the host.  --window-only times the
 window alone (the script then needs nothing newer than hm_stream_window, so a
 checkout of an earlier commit can run it on the same log); --parent-json FILE
 puts that run's "window" into this one's result as "parent_window".
+
+    python tools/bench_stream.py --retain 24 --batches 30 --warmup 0 --snapshot --out profiles/stream_snapshot.json
+
+--snapshot: on the steady retained log, hm_stream_export of the whole log and
+hm_stream_import of that export into a fresh stream whose log is sized for it
+(7 interleaved repetitions after one warm-up pair, host ms around the C call,
+median and range, and the effective GB/s over 40 B per cell), one save() +
+load() round trip through a file, and the only restore there is without
+snapshots: the retained one-hour batches of raw points added again to a fresh
+stream (3 repetitions).  "check": every restored stream's window over the
+retained hours and its cell count equal the original's.  The yardsticks of the
+same session are in the same JSON line: "ms_expire" (the nearest existing pass
+over the same log) and "read_stream_GBps".  --readd-only times the re-adding
+alone (nothing newer than hm_stream_window is needed, so a checkout of the
+parent commit can run it); --parent-json FILE puts that run's "readd_ms" into
+this one's result as "parent_readd_ms".
 """
 import argparse
 import json
@@ -153,6 +169,115 @@ def view_bench(s, a, lo, hi):
     return out
 
 
+SNAP_REPS = 7
+READD_REPS = 3
+
+
+def _sorted_cells(n, keys, counts):
+    k, order = torch.sort(keys[:n])
+    return k, counts[:n][order]
+
+
+def readd_bench(a, lat, lon, retained, cap):
+    """the restore a user has without snapshots: the retained one-hour batches
+    of raw points added again to a fresh stream whose log is sized for them
+    (READD_REPS fresh streams; the last one is returned for the check)"""
+    pool, n = len(lat), int(a.batch)
+    hours = [torch.full((n,), BASE + b, dtype=torch.int32, device="cuda") for b in retained]
+    t, s2 = [], None
+    for _ in range(READD_REPS):
+        if s2 is not None:
+            s2.close()
+        s2 = StreamingHeatmap(a.zmin, a.zmax, base_hour=BASE, initial_cells=cap)
+        t.append(_ms(lambda: [s2.add(lat[b % pool], lon[b % pool], hour=h) for b, h in zip(retained, hours)])[0])
+    return t, s2
+
+
+def snapshot_bench(s, a, lat, lon, retained):
+    """--snapshot (module docstring) on the stream as it stands"""
+    import ctypes
+    import shutil
+    import tempfile
+
+    from heatmap_amd import _lib
+
+    lo, hi = BASE + retained[0], BASE + retained[-1] + 1
+    n, cap = s.cells()
+    out = {"hours": [lo, hi], "log_cells": n, "log_capacity": cap, "batches_retained": len(retained),
+           "timing": "host ms around the call (ends in a synchronise); export and import interleaved"}
+    t_readd, s2 = readd_bench(a, lat, lon, retained, cap)
+    out["readd_ms"] = _stats(t_readd)
+    out["readd_note"] = "%d hm_stream_add calls of %d raw points each into a fresh stream" % (len(retained), int(a.batch))
+    wn, wk, wc, _ = s.window_device(lo, hi)
+    want = _sorted_cells(wn, wk, wc)
+    del wk, wc
+
+    def same_window(x):
+        xn, xk, xc, _ = x.window_device(lo, hi)
+        if xn != wn:
+            return False
+        got = _sorted_cells(xn, xk, xc)
+        return bool(torch.equal(got[0], want[0]) and torch.equal(got[1], want[1]))
+
+    ok = same_window(s2) and s2.cells()[0] == n
+    s2.close()
+    if a.readd_only:
+        out["check"] = "ok" if ok else "FAIL"
+        return out
+    L = s.ctx.L
+    keys = torch.empty(n, dtype=torch.int64, device="cuda")
+    counts = torch.empty(n, dtype=torch.int64, device="cuda")
+    groups = torch.empty(n, dtype=torch.int32, device="cuda")
+    hours = torch.empty(n, dtype=torch.int32, device="cuda")
+    m = ctypes.c_int64(0)
+
+    def export():
+        rc = L.hm_stream_export(s.ptr, keys.data_ptr(), counts.data_ptr(), groups.data_ptr(), hours.data_ptr(), n,
+                                ctypes.byref(m))
+        assert rc == 0 and m.value == n, (rc, m.value)
+
+    def imported(x):
+        rc = L.hm_stream_import(x.ptr, keys.data_ptr(), counts.data_ptr(), groups.data_ptr(), hours.data_ptr(), n,
+                                _lib.HM_IMPORT_DISTINCT)
+        assert rc == 0, rc
+
+    t_exp, t_imp, s3 = [], [], None
+    for rep in range(SNAP_REPS + 1):        # the first pair warms up and is dropped
+        if s3 is not None:
+            s3.close()
+        s3 = StreamingHeatmap(a.zmin, a.zmax, base_hour=BASE, initial_cells=cap)
+        t_exp.append(_ms(export)[0])
+        t_imp.append(_ms(lambda: imported(s3))[0])
+        print("snapshot rep %d: export %.2f ms, import %.2f ms" % (rep, t_exp[-1], t_imp[-1]), file=sys.stderr, flush=True)
+    out["export_ms"], out["import_ms"] = _stats(t_exp[1:]), _stats(t_imp[1:])
+    out["export_GBps"] = 40.0 * n / (out["export_ms"]["median"] * 1e-3) / 1e9
+    out["import_GBps"] = 40.0 * n / (out["import_ms"]["median"] * 1e-3) / 1e9
+    out["bytes"] = ("export: 16 B per log cell read + 24 B written (key, count, group, hour); import: the same 24 B "
+                    "read + 16 B written at the log's tail")
+    ok = ok and same_window(s3) and s3.cells()[0] == n
+    s3.close()
+    del keys, counts, groups, hours
+    tmp = tempfile.mkdtemp(prefix="hm_snapshot_")
+    try:
+        path = os.path.join(tmp, "stream.npz")
+        out["save_ms"] = _ms(lambda: s.save(path))[0]
+        out["file_bytes"] = os.path.getsize(path)
+        print("snapshot saved: %.0f ms, %d bytes" % (out["save_ms"], out["file_bytes"]), file=sys.stderr, flush=True)
+        out["load_ms"], s4 = _ms(lambda: StreamingHeatmap.load(path, initial_cells=cap))
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+    ok = ok and same_window(s4) and s4.cells()[0] == n
+    s4.close()
+    out["check"] = "ok" if ok else "FAIL"
+    if a.parent_json:
+        pj = json.load(open(a.parent_json))["snapshot"]
+        assert pj["log_cells"] == n and pj["check"] == "ok" and pj["hours"] == [lo, hi]
+        out["parent_readd_ms"] = pj["readd_ms"]
+        out["parent_readd_note"] = ("this script with --readd-only run by a checkout of the parent commit (its library "
+                                    "and package) on the same seeded batches, in the same session")
+    return out
+
+
 def retain(a):
     """--retain H: a stream under retention (module docstring)"""
     n, H = int(a.batch), a.retain
@@ -182,6 +307,7 @@ def retain(a):
                 gbps.append(16.0 * (2 * llen - dropped) / (ms_exp * 1e-3) / 1e9)
     steady = [x for x in series if x["batch"] > H]
     view = view_bench(s, a, BASE + total - 1 - H, BASE + total) if a.view else None
+    snap = snapshot_bench(s, a, lat, lon, list(range(total - 1 - H, total))) if a.snapshot or a.readd_only else None
     result = json.dumps({
         "metric": "stream under retention: expire(newest - H) and window(newest - H, newest + 1) per one-hour batch",
         "retain_hours": H, "batch_points": n, "batches": a.batches, "warmup": a.warmup, "zooms": [a.zmin, a.zmax],
@@ -195,6 +321,7 @@ def retain(a):
                          "cells_min_max": [min(x["cells"] for x in steady), max(x["cells"] for x in steady)]}
         if steady else None,
         "view": view,
+        "snapshot": snap,
         "series": series,
         "data": "synthetic (heatmap_amd.synth, generated on device, resident in HBM)"})
     print(result)
@@ -220,8 +347,13 @@ def main():
     ap.add_argument("--view", action="store_true",
                     help="with --retain: window vs viewport queries on the steady log (module docstring)")
     ap.add_argument("--window-only", action="store_true", help="with --view: time the window alone")
+    ap.add_argument("--snapshot", action="store_true",
+                    help="with --retain: export, import and save/load of the steady log (module docstring)")
+    ap.add_argument("--readd-only", action="store_true",
+                    help="with --retain: time only the re-adding of the retained batches to a fresh stream")
     ap.add_argument("--parent-json", default=None, metavar="FILE",
-                    help="with --view: a --window-only result of the parent commit, kept as parent_window")
+                    help="with --view: a --window-only result of the parent commit, kept as parent_window; with "
+                         "--snapshot: its --readd-only result, kept as parent_readd_ms")
     ap.add_argument("--out", default=None, metavar="FILE", help="with --retain: also write the JSON line to FILE")
     a = ap.parse_args()
     if a.retain > 0:
