@@ -1088,6 +1088,9 @@ static int count_impl(hm_ctx* ctx, const double* lat, const double* lon, const i
                     HIPCHK(hipMemsetAsync(ctx->state + ST_OVERFLOW, 0, 8, s));
                     HIPCHK(hipMemsetAsync(xl.count, 0, 8, s));
                     HIPCHK(hipMemsetAsync(ctx->state + ST_NSLOTS, 0, 8, s));   /* buckets1 again */
+                    /* hm_last_stats: the points this run resolves, not those
+                     * plus the first run's deferred ones (every point twice) */
+                    HIPCHK(hipMemsetAsync(ctx->state + ST_SLOW, 0, 8, s));
                     hm_launch_part1(s, a, tiles_in, V.out16, 2);
                     HIPCHK(hipGetLastError());
                     if ((st = buckets1())) return st;

@@ -23,6 +23,7 @@
 #define HM_UNLIKELY(x) __builtin_expect(!!(x), 0)
 #else
 #include <math.h>
+#include <stdbool.h>
 #include <string.h>
 #define HM_EMUL_FN static inline
 #define HM_EMUL_TABLE static const

@@ -778,31 +778,10 @@ k_l1_fast(HmPart1Args a)
     for (int k = 0; k < HM_P1_PPT; k++) {
         const double pa = (k & 1) ? la[k >> 1].y : la[k >> 1].x;
         const double po = (k & 1) ? lo[k >> 1].y : lo[k >> 1].x;
-        /* row: Y = 1/2 - sign(lat) g(90 - |lat|) (hm_fast_g), R = Y 2^Z */
-        const double dd = 90.0 - fabs(pa);
-        const uint32_t dh = (uint32_t)(hm_d2u(dd) >> 32);
-        constexpr uint32_t I0 = (1023u + HM_YTAB_E0) << HM_YTAB_K;
-        const uint32_t ii = min((dh >> (20 - HM_YTAB_K)) - I0, (uint32_t)HM_YTAB_ROWS);   /* wraps below d = 4 */
-        const double dlo = hm_u2d((uint64_t)(dh & ~((1u << (20 - HM_YTAB_K)) - 1u)) << 32);
-        const double t = dd - dlo;
-        const double* cf = tab + ii * HM_YTAB_STRIDE;
-        double p = cf[5];
-        p = fma(p, t, cf[4]);
-        p = fma(p, t, cf[3]);
-        p = fma(p, t, cf[2]);
-        p = fma(p, t, cf[1]);
-        p = fma(p, t, cf[0]);
-        const double R = fma(copysign(p, pa), nscale, hscale);
-        const double fr = __builtin_amdgcn_fract(R);
-        /* column: y = (lon + 180) / 360 * 2^z within 2^(z-51.3); guard 2^(z-49) */
-        const double y = fma(po, kz, c180);
-        const double fc = __builtin_amdgcn_fract(y);
-        /* |lat| <= HM_LAT_SQ as dd >= 90 - HM_LAT_SQ: both differences are
-         * exact for |lat| in [45, 180] (Sterbenz), dd >= 45 below, NaN fails */
-        const bool ok = (int)(dd >= 90.0 - HM_LAT_SQ) & (int)(fabs(fr - 0.5) < ghalf) & (int)(fabs(po) < 180.0) &
-                        (int)(fabs(fc - 0.5) < ghalf2);
-        const uint32_t r = (uint32_t)(int32_t)R;   /* truncation = floor: R, y > 0 when ok */
-        const uint32_t c = (uint32_t)(int32_t)y;
+        /* the projection's own statements: hm_project.h, compiled for the
+         * CPU tests too */
+        uint32_t r, c;
+        const bool ok = hm_project_l1(pa, po, nscale, hscale, kz, c180, ghalf, ghalf2, tab, &r, &c);
         const bool kept = ((kp[k >> 1] >> (8 * (k & 1))) & 0xFFu) != 0;
         redo |= (uint32_t)!ok << k;
         /* cold slot: bank-skewed z1 digit above the hot slots */

@@ -170,6 +170,83 @@ HM_FN int hm_project_fast(double lat, double lon, double scale, double kz, int32
     return ok;
 }
 
+/* x - floor(x) in [0, 1): one v_fract_f64 on the device (the hardware clamps
+ * the difference below 1; NaN stays NaN).  The host form clamps likewise, and
+ * turns inf - inf into NaN where the instruction gives 0: either fails every
+ * |frac - 1/2| < g test. */
+HM_FN double hm_fract(double x)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_fract(x);
+#else
+    const double f = x - floor(x);
+    return f < 1.0 ? f : (f != f ? f : 0x1.fffffffffffffp-1);
+#endif
+}
+
+/* (uint32_t)(int32_t)x: the device's convert truncates and saturates (NaN: 0);
+ * the host restates that, where the C conversion of such a value is undefined */
+HM_FN uint32_t hm_trunc_u32(double x)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return (uint32_t)(int32_t)x;
+#else
+    if (x != x) return 0u;
+    if (x >= 2147483647.0) return 0x7FFFFFFFu;
+    if (x <= -2147483648.0) return 0x80000000u;
+    return (uint32_t)(int32_t)x;
+#endif
+}
+
+/* The whole-tile level-1 kernel's projection (k_l1_fast, hm_kernels.hip):
+ * the decision of hm_project_fast -- accept the fast tile or defer the point
+ * to the exact chain -- with fewer instructions per point:
+ *   row     hm_fast_g restated with the index clamped to row HM_YTAB_ROWS, one
+ *           spare row behind the table (the kernel keeps NaN there, for the
+ *           wrapped index of d < 4, |lat| > 90 and NaN; any value serves, the
+ *           latitude test rejects those points); the fraction is hm_fract and
+ *           the floor a truncation (R, y > 0 when ok);
+ *   column  one fma, y = lon kz + 180 kz, inside the same 2^-49 guard; the
+ *           range test is |lon| < 180 on the input (an accepted y lies in
+ *           [0, 2^z));
+ *   square  |lat| <= HM_LAT_SQ as dd >= 90 - HM_LAT_SQ: both differences are
+ *           exact for |lat| in [45, 180] (Sterbenz), dd >= 45 below, NaN fails.
+ * Per-launch constants: nscale = -2^z, hscale = 2^z / 2, kz = RN(1/360) 2^z,
+ * c180 = 180 kz, ghalf = 1/2 - HM_Y_EPS 2^z, ghalf2 = 1/2 - 2^(z-49).  tab
+ * holds HM_YTAB_ROWS + 1 rows.  Returns ok; *r, *c are the tile when ok and
+ * unspecified otherwise.  tests/host_math compiles these statements for the
+ * CPU suite (hmh_project_l1). */
+HM_FN __attribute__((always_inline)) bool hm_project_l1(double pa, double po, double nscale, double hscale, double kz,
+                                                       double c180, double ghalf, double ghalf2, const double* tab,
+                                                       uint32_t* r, uint32_t* c)
+{
+    /* row: Y = 1/2 - sign(lat) g(90 - |lat|) (hm_fast_g), R = Y 2^Z */
+    const double dd = 90.0 - fabs(pa);
+    const uint32_t dh = (uint32_t)(hm_d2u(dd) >> 32);
+    const uint32_t I0 = (1023u + HM_YTAB_E0) << HM_YTAB_K;
+    uint32_t ii = (dh >> (20 - HM_YTAB_K)) - I0;   /* wraps below d = 4 */
+    ii = ii < (uint32_t)HM_YTAB_ROWS ? ii : (uint32_t)HM_YTAB_ROWS;
+    const double dlo = hm_u2d((uint64_t)(dh & ~((1u << (20 - HM_YTAB_K)) - 1u)) << 32);
+    const double t = dd - dlo;
+    const double* cf = tab + ii * HM_YTAB_STRIDE;
+    double p = cf[5];
+    p = fma(p, t, cf[4]);
+    p = fma(p, t, cf[3]);
+    p = fma(p, t, cf[2]);
+    p = fma(p, t, cf[1]);
+    p = fma(p, t, cf[0]);
+    const double R = fma(copysign(p, pa), nscale, hscale);
+    const double fr = hm_fract(R);
+    /* column: y = (lon + 180) / 360 * 2^z within 2^(z-51.3); guard 2^(z-49) */
+    const double y = fma(po, kz, c180);
+    const double fc = hm_fract(y);
+    const bool ok = (int)(dd >= 90.0 - HM_LAT_SQ) & (int)(fabs(fr - 0.5) < ghalf) & (int)(fabs(po) < 180.0) &
+                   (int)(fabs(fc - 0.5) < ghalf2);
+    *r = hm_trunc_u32(R);   /* truncation = floor: R, y > 0 when ok */
+    *c = hm_trunc_u32(y);
+    return ok;
+}
+
 /* tile_id_from_lat_long order: row first, its error wins (tile.py:10-11). */
 HM_FN int hm_project_point(double lat, double lon, int zoom, int64_t* row, int64_t* col, int* slow,
                            const double* tab)

@@ -20,6 +20,8 @@ What it calls (all read-only, no bytecode written into the reference dir):
 
 Outputs (data only -- inputs and the reference's outputs):
   projection_kat.npz        lat, lon, zoom -> row/col or error kind
+  projection_edges.npz      the edge catalogue of tests/proj_edges.py at zooms
+                            0, 3, 14, 18, 21, 30 (--only edges)
   tile_ids.json             a few hundred formatted "z_r_c" strings
   heatmap_rows_*.json.gz    build_heatmaps rows for small mixed datasets
   config1_digest.json       1M uniform points: per-zoom counts / digests
@@ -220,6 +222,51 @@ def projection_kat(Tile, rng):
     with open(os.path.join(HERE, "tile_ids.json"), "w") as f:
         json.dump([[repr(a), repr(b), z, s] for a, b, z, s in ids], f)
     print("projection KATs:", n, "errors(row):", int((row_err != 0).sum()), "boundary cases included")
+
+
+EDGE_ZOOMS = (0, 3, 14, 18, 21, 30)
+EDGE_MAX_BYTES = 1000 * 1000          # a committed file stays below 1 MiB
+
+
+def projection_edges(Tile):
+    """The reference's Tile on the edge catalogue (tests/proj_edges.py) at
+    EDGE_ZOOMS: projection_kat.npz's fields, with lat/lon held once and one row
+    of row/col/row_err/col_err per zoom.  The named edges are always all
+    there; the seeded random pairs after them are cut to what fits the size
+    limit."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    import proj_edges
+
+    lat, lon = proj_edges.project_set()
+    n = lat.size
+    row = np.zeros((len(EDGE_ZOOMS), n), np.int64)
+    col = np.zeros((len(EDGE_ZOOMS), n), np.int64)
+    row_err = np.zeros((len(EDGE_ZOOMS), n), np.int8)
+    col_err = np.zeros((len(EDGE_ZOOMS), n), np.int8)
+    la, lo = lat.tolist(), lon.tolist()
+    for k, z in enumerate(EDGE_ZOOMS):
+        for i in range(n):
+            e, r = classify(lambda: Tile.row_from_latitude(la[i], z))
+            row_err[k, i] = e
+            row[k, i] = r if e == OK else 0
+            e, c = classify(lambda: Tile.column_from_longitude(lo[i], z))
+            col_err[k, i] = e
+            if e == OK:
+                if -(1 << 63) <= c < (1 << 63):
+                    col[k, i] = c
+                else:
+                    col_err[k, i] = 8         # exceeds int64
+    path = os.path.join(HERE, "projection_edges.npz")
+    m = n
+    while True:
+        np.savez_compressed(path, lat=lat[:m], lon=lon[:m], zoom=np.array(EDGE_ZOOMS, np.int8), row=row[:, :m],
+                            col=col[:, :m], row_err=row_err[:, :m], col_err=col_err[:, :m])
+        size = os.path.getsize(path)
+        if size <= EDGE_MAX_BYTES or m == proj_edges.n_named():
+            break
+        m = max(proj_edges.n_named(), int(m * EDGE_MAX_BYTES / size * 0.97))
+    print("projection edges:", m, "of", n, "points (named:", proj_edges.n_named(), ")", size, "bytes; errors(row):",
+          int((row_err[:, :m] != 0).sum()))
 
 
 def run_build_heatmaps(hm, rows, max_zoom_level=16, delta=5):
@@ -498,6 +545,8 @@ def main():
     todo = a.only.split(",") if a.only else ["kat", "rows", "hot", "c1"]
     if "kat" in todo:
         projection_kat(Tile, rng)
+    if "edges" in todo or not a.only:
+        projection_edges(Tile)
     if "rows" in todo:
         heatmap_goldens(hm, rng)
     if "hot" in todo:

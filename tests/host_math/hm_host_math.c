@@ -70,6 +70,32 @@ int64_t hmh_glibc_check(int fn, const double* x, int64_t n, int64_t* unsupported
     return bad;
 }
 
+/* k_l1_fast's projection (hm_project_l1) with the kernel's per-launch
+ * constants; the table has one spare zero row, which the clamped index of
+ * d < 4, |lat| > 90 and NaN reads (the kernel keeps NaN there: either is
+ * rejected by the latitude test).  row32/col32 are 0 where ok[i] is 0. */
+static const double TAB_L1[(HM_YTAB_ROWS + 1) * HM_YTAB_STRIDE] = HM_YTAB_INIT;
+
+int64_t hmh_project_l1(const double* lat, const double* lon, int64_t n, int zoom, int32_t* row32, int32_t* col32,
+                       uint8_t* ok)
+{
+    const double scale = hm_exp2i(zoom);
+    const double nscale = -scale, hscale = 0.5 * scale;
+    const double kz = HM_INV360 * scale;
+    const double c180 = 180.0 * kz;
+    const double ghalf = 0.5 - HM_Y_EPS * scale;
+    const double ghalf2 = 0.5 - scale * 0x1p-49;
+    int64_t m = 0;
+    for (int64_t i = 0; i < n; i++) {
+        uint32_t r = 0, c = 0;
+        ok[i] = (uint8_t)hm_project_l1(lat[i], lon[i], nscale, hscale, kz, c180, ghalf, ghalf2, TAB_L1, &r, &c);
+        row32[i] = ok[i] ? (int32_t)r : 0;
+        col32[i] = ok[i] ? (int32_t)c : 0;
+        m += ok[i];
+    }
+    return m;
+}
+
 /* the streaming kernels' branch-free fast path (ok[i] = 1 where conclusive) */
 int64_t hmh_project_fast(const double* lat, const double* lon, int64_t n, int zoom, int32_t* row, int32_t* col,
                          uint8_t* ok)
