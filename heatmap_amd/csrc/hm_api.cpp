@@ -171,6 +171,7 @@ enum {
     B_HOT, B_HOT_COUNTS, B_HOT_PARENT, B_D2B, B_MB_CNT, B_MB_OFF, B_MB_KEYS, B_MB_COUNTS, B_MB_CNT2, B_MB_OFF2,
     B_MB_KEYS2, B_MB_COUNTS2, B_KEYS_C, B_HOT_FORCE, B_C2B, B_SEG2, B_CTOT, B_CBASE, B_CCUR, B_MG_PIECES,
     B_L1_SLOT,
+    B_RS_B, B_RS_MX,   /* hm_raster_render: blurred counts, the two maxima */
     B_COUNT
 };
 
@@ -3136,6 +3137,146 @@ extern "C" int hm_stream_view(hm_stream* s, int64_t hour_lo, int64_t hour_hi, in
     a.gmode = group == HM_VIEW_MERGED ? HMS_VIEW_MERGED : (group == HM_VIEW_EACH ? HMS_VIEW_EACH : HMS_VIEW_GROUP);
     a.group = group >= 0 ? (uint32_t)group : 0u;
     return stream_view(s, a, keys_out, counts_out, groups_out, capacity, n_out);
+}
+
+/* ---- rasters: dense tile grids and rendered tiles (hm_raster.hip) ---- */
+
+/* the shared argument check of the two scatters: tiles inside their squares,
+ * bin zooms inside [zlo, zhi] */
+static bool raster_args_ok(const int64_t* tiles, int ntiles, int bins_log2, int halo, int zlo, int zhi)
+{
+    if (!tiles || ntiles < 1 || ntiles > HM_RASTER_MAX_TILES || bins_log2 < 0 || bins_log2 > HM_RASTER_MAX_BINS_LOG2 ||
+        halo < 0 || halo > HM_RASTER_MAX_HALO)
+        return false;
+    for (int t = 0; t < ntiles; t++) {
+        const int64_t tz = tiles[3 * t], tr = tiles[3 * t + 1], tc = tiles[3 * t + 2];
+        if (tz < 0 || tz > HM_MAX_ZOOM || tz + bins_log2 < zlo || tz + bins_log2 > zhi) return false;
+        if (tr < 0 || tc < 0 || tr >= (1ll << tz) || tc >= (1ll << tz)) return false;
+    }
+    return true;
+}
+
+extern "C" int hm_stream_raster(hm_stream* s, int64_t hour_lo, int64_t hour_hi, int64_t group, const int64_t* tiles,
+                                int ntiles, int bins_log2, int halo, uint64_t* grid_out)
+{
+    const bool alltime = hour_lo == HM_STREAM_ALLTIME && hour_hi == HM_STREAM_ALLTIME;
+    if (!s || !grid_out || (!alltime && hour_hi <= hour_lo) || group < HM_VIEW_MERGED || group > (int64_t)HMS_NOGROUP ||
+        !raster_args_ok(tiles, ntiles, bins_log2, halo, s->zmin, s->zmax))
+        return HM_E_ARG;
+    hm_ctx* ctx = s->ctx;
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t q = ctx->stream;
+    const int64_t S = 1ll << bins_log2, W = S + 2 * halo;
+    HIPCHK(hipMemsetAsync(grid_out, 0, (size_t)ntiles * W * W * 8, q));
+    HmsRasterArgs a;
+    a.alltime = alltime ? 1 : 0;
+    a.lo = a.hi = 0;
+    if (!alltime) {
+        a.lo = stream_hour_offset(s, hour_lo), a.hi = stream_hour_offset(s, hour_hi);
+        if (a.lo >= a.hi) return HM_OK;   /* all of it outside the stream's hours */
+    }
+    if (s->llen == 0) return HM_OK;
+    uint64_t box_hi = 0;
+    a.box_lo = ~0ull;
+    for (int t = 0; t < ntiles; t++) {
+        const int64_t z = tiles[3 * t] + bins_log2, side = 1ll << z;
+        const int64_t oy = (tiles[3 * t + 1] << bins_log2) - halo, ox = (tiles[3 * t + 2] << bins_log2) - halo;
+        /* the haloed square clipped to [0, 2^z)^2: never empty, the tile itself is inside */
+        const int64_t rlo = std::max<int64_t>(oy, 0), rhi = std::min<int64_t>(oy + W, side);
+        const int64_t clo = std::max<int64_t>(ox, 0), chi = std::min<int64_t>(ox + W, side);
+        HmsRasterRect& R = a.rects[t];
+        R.id_lo = ((1ull << (2 * z)) - 1ull) / 3ull + ((uint64_t)rlo << z);
+        R.span = (uint64_t)(rhi - rlo) << z;
+        R.col_lo = (uint32_t)clo;
+        R.col_w = (uint32_t)(chi - clo);
+        R.z = (uint8_t)z;
+        R.y0 = (uint8_t)(rlo - oy);
+        R.x0 = (uint8_t)(clo - ox);
+        R.pad0 = 0;
+        R.pad = 0;
+        a.box_lo = std::min(a.box_lo, R.id_lo);
+        box_hi = std::max(box_hi, R.id_lo + R.span);
+    }
+    a.box_span = box_hi - a.box_lo;
+    a.keys = s->lkeys;
+    a.counts = s->lcounts;
+    a.n = s->llen;
+    a.buckets = s->bk;
+    a.cb = s->cb;
+    a.ntiles = ntiles;
+    a.gmode = group == HM_VIEW_MERGED ? HMS_VIEW_MERGED : HMS_VIEW_GROUP;
+    a.group = group >= 0 ? (uint32_t)group : 0u;
+    a.W = (uint32_t)W;
+    a.grid = (unsigned long long*)grid_out;
+    hm_launch_stream_raster(q, a);
+    HIPCHK(hipGetLastError());
+    return HM_OK;
+}
+
+extern "C" int hm_cells_raster(hm_ctx* ctx, const uint64_t* keys, const uint64_t* counts, int64_t n,
+                               const int64_t* tiles, int ntiles, int bins_log2, int halo, uint64_t* grid_out)
+{
+    if (!ctx || !grid_out || n < 0 || (n > 0 && (!keys || !counts)) ||
+        !raster_args_ok(tiles, ntiles, bins_log2, halo, 0, HM_MAX_ZOOM))
+        return HM_E_ARG;
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t q = ctx->stream;
+    const int64_t S = 1ll << bins_log2, W = S + 2 * halo;
+    HIPCHK(hipMemsetAsync(grid_out, 0, (size_t)ntiles * W * W * 8, q));
+    if (n == 0) return HM_OK;
+    HmCellsRasterArgs a;
+    a.keys = keys;
+    a.counts = counts;
+    a.n = (uint64_t)n;
+    a.ntiles = ntiles;
+    a.W = (uint32_t)W;
+    a.grid = (unsigned long long*)grid_out;
+    for (int t = 0; t < ntiles; t++) {
+        a.tiles[t].z = (int32_t)(tiles[3 * t] + bins_log2);
+        a.tiles[t].oy = (int32_t)((tiles[3 * t + 1] << bins_log2) - halo);
+        a.tiles[t].ox = (int32_t)((tiles[3 * t + 2] << bins_log2) - halo);
+    }
+    hm_launch_cells_raster(q, a);
+    HIPCHK(hipGetLastError());
+    return HM_OK;
+}
+
+extern "C" int hm_raster_render(hm_ctx* ctx, const uint64_t* grid, int ntiles, int bins_log2, int halo, int radius,
+                                int scale, uint64_t vmax, const uint32_t* lut, uint8_t* rgba_out, uint8_t* levels_out,
+                                uint64_t* vmax_used)
+{
+    if (!ctx || !grid || !lut || !rgba_out || ((uintptr_t)rgba_out & 3) || ntiles < 1 || ntiles > HM_RASTER_MAX_TILES ||
+        bins_log2 < 0 || bins_log2 > HM_RASTER_MAX_BINS_LOG2 || halo < 0 || halo > HM_RASTER_MAX_HALO || radius < 0 ||
+        radius > halo || (scale != HM_SCALE_LINEAR && scale != HM_SCALE_LOG))
+        return HM_E_ARG;
+    const uint64_t wide = 1ull << (56 - 4 * radius);
+    if (vmax >= wide) return HM_E_ARG;
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t q = ctx->stream;
+    HmRenderArgs a;
+    a.grid = grid;
+    a.ntiles = ntiles;
+    a.bins_log2 = bins_log2;
+    a.halo = halo;
+    a.radius = radius;
+    a.scale = scale;
+    a.vs = vmax << (4 * radius);
+    a.wide = wide;
+    ENSURE(B_RS_B, ((size_t)ntiles << (2 * bins_log2)) * 8, a.B);
+    ENSURE(B_RS_MX, 16, a.mx);
+    a.lut = lut;
+    a.rgba = (uint32_t*)rgba_out;
+    a.levels = levels_out;
+    HIPCHK(hipMemsetAsync(a.mx, 0, 16, q));
+    hm_launch_raster_blur(q, a);
+    hm_launch_raster_colour(q, a);
+    HIPCHK(hipGetLastError());
+    unsigned long long* down = ctx->host_state + 2 * ST_COUNT;
+    HIPCHK(hipMemcpyAsync(down, a.mx, 16, hipMemcpyDeviceToHost, q));
+    HIPCHK(hm_sync(q));
+    if (down[0] >= wide) return HM_E_WIDE;
+    if (vmax_used) *vmax_used = a.vs ? a.vs : (uint64_t)down[1];
+    return HM_OK;
 }
 
 extern "C" int hm_stream_expire(hm_stream* s, int64_t before_hour, int64_t* cells_dropped, int64_t* buckets_freed)

@@ -635,6 +635,67 @@ struct HmsViewArgs {
     unsigned long long* state;
     HmsViewRect rects[HMS_VIEW_MAX_RECTS];   /* by value: wave-uniform, read as scalars */
 };
+/* a raster query: the log's cells of the wanted hours and group added into
+ * dense per-tile grids (k_stream_raster).  A tile's haloed square, clipped to
+ * [0, 2^z)^2, is a view rectangle (id interval + column window) plus where its
+ * first row and column land in the tile's (S + 2 halo)^2 grid; grid t starts
+ * at grid + t * W * W. */
+#define HMS_RASTER_MAX_TILES 64
+struct HmsRasterRect {
+    uint64_t id_lo;          /* off(z) + (first clipped row << z) */
+    uint64_t span;           /* clipped rows << z */
+    uint32_t col_lo, col_w;  /* clipped columns */
+    uint8_t z, y0, x0, pad0; /* zoom; grid row / column of the first clipped row / column */
+    uint32_t pad;
+};
+struct HmsRasterArgs {
+    const uint64_t* keys;    /* the log */
+    const uint64_t* counts;
+    uint64_t n;
+    HmsBuckets buckets;
+    int cb, ntiles, gmode, alltime;   /* gmode: HMS_VIEW_MERGED or HMS_VIEW_GROUP */
+    uint32_t lo, hi;         /* dated hour offsets lo <= hour - base < hi */
+    uint32_t group;
+    uint32_t W;              /* grid side S + 2 halo */
+    uint64_t box_lo, box_span;
+    unsigned long long* grid;
+    HmsRasterRect rects[HMS_RASTER_MAX_TILES];   /* by value (2 KB): wave-uniform, read as scalars */
+};
+void hm_launch_stream_raster(hipStream_t s, const HmsRasterArgs& a);
+/* the same scatter from cells in hm_count's key layout (hm_raster.hip); a
+ * tile's grid origin may lie outside the square (oy, ox < 0) */
+struct HmRasterTile {
+    int32_t z, oy, ox;       /* bin zoom tz + bins_log2; row / column of grid element [0][0] */
+};
+struct HmCellsRasterArgs {
+    const uint64_t* keys;
+    const uint64_t* counts;
+    uint64_t n;
+    int ntiles;
+    uint32_t W;
+    unsigned long long* grid;
+    HmRasterTile tiles[HMS_RASTER_MAX_TILES];
+};
+void hm_launch_cells_raster(hipStream_t s, const HmCellsRasterArgs& a);
+/* blur + normalise + colour (hm_raster.hip): pass 1 writes the blurred counts
+ * B and the two maxima (mx[0]: raw g over the haloed grids, mx[1]: B over the
+ * interiors, both zeroed by the caller), pass 2 maps B to level and colour
+ * unless mx[0] >= wide */
+#define HM_BLUR_BLOCK 32                 /* outputs per side of a blur block */
+struct HmRenderArgs {
+    const uint64_t* grid;
+    int ntiles, bins_log2, halo, radius, scale;
+    uint64_t vs;             /* fixed scale unit, or 0: mx[1] */
+    uint64_t wide;           /* 2^(56 - 4 radius) */
+    uint64_t* B;             /* [ntiles][S][S] */
+    unsigned long long* mx;
+    const uint32_t* lut;
+    uint32_t* rgba;
+    uint8_t* levels;         /* or NULL */
+};
+void hm_launch_raster_blur(hipStream_t s, const HmRenderArgs& a);
+void hm_launch_raster_colour(hipStream_t s, const HmRenderArgs& a);
+
 /* merged label cells -> caller's arrays (k_stream_emit) */
 struct HmsEmitArgs {
     const uint64_t* keys;

@@ -29,6 +29,8 @@
  * rule on the same chain.  A viewport (hm_stream_view) swaps the relabel for
  * k_stream_view, which keeps only the cells inside a few rectangles, tested on
  * the key alone, so merge and emit see the viewport's cells, not the window's.
+ * A raster (hm_stream_raster, k_stream_raster) is that filter followed by adds
+ * into dense per-tile grids: equal cells meet in one bin, so nothing is merged.
  * Retention (hm_stream_expire, k_stream_expire)
  * filters the log into the alternate arrays and moves the surviving buckets
  * to a fresh bucket table, which frees the slots of the expired hours and of
@@ -621,6 +623,83 @@ __global__ __launch_bounds__(256) void k_stream_view(HmsViewArgs a)
     }
 }
 
+/* is a raw bucket key inside a raster's hours and group */
+__device__ __forceinline__ bool hms_raster_in(const HmsRasterArgs& a, uint64_t bk)
+{
+    const uint32_t pw = (uint32_t)bk, g = (uint32_t)(bk >> 32);
+    const bool dated = (pw >> 28) == 0;
+    const bool in = a.alltime ? (dated || pw == HMS_UNDATED) : (dated && pw >= a.lo && pw < a.hi);
+    return in && (a.gmode != HMS_VIEW_GROUP || g == a.group);
+}
+
+/* A raster query: k_stream_view's filter (HMS_VW_U keys in flight, the common
+ * interval test, a bucket read for the cells inside a rectangle only, a count
+ * read for the survivors only) with nothing after it but the adds: equal cells
+ * of different hours and groups land in the same bin, so there is no label,
+ * no intern, no ranking and no cursor.  A cell is added to the grid of every
+ * tile whose haloed square holds it (the rectangles of neighbour tiles
+ * overlap by their halos; a repeated tile is its own grid), one non-returning
+ * 64-bit atomic each; the survivors follow the viewport, not the log. */
+__global__ __launch_bounds__(256) void k_stream_raster(HmsRasterArgs a)
+{
+    constexpr int U = HMS_VW_U;
+    const int tid = threadIdx.x;
+    const uint64_t cmask = (1ull << a.cb) - 1ull;
+    const uint32_t WW = a.W * a.W;
+    constexpr uint64_t CH = 256 * U;
+    for (uint64_t c0 = (uint64_t)blockIdx.x * CH; c0 < a.n; c0 += (uint64_t)gridDim.x * CH) {
+        uint64_t k[U];
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const uint64_t i = c0 + (uint64_t)u * 256 + tid;
+            k[u] = i < a.n ? a.keys[i] : 0ull;
+        }
+        uint32_t box = 0;             /* bit u: cell u lies in the rectangles' common interval */
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const uint64_t i = c0 + (uint64_t)u * 256 + tid;
+            box |= (uint32_t)(i < a.n && (k[u] & cmask) - a.box_lo < a.box_span) << u;
+        }
+        if (!__ballot(box != 0)) continue;
+        uint32_t hit = 0;             /* bit u: cell u lies in a rectangle */
+        for (int r = 0; r < a.ntiles; r++) {
+            const HmsRasterRect R = a.rects[r];
+            const uint32_t zmask = (1u << R.z) - 1u;
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+                const uint64_t d = (k[u] & cmask) - R.id_lo;
+                hit |= (uint32_t)(d < R.span && ((uint32_t)d & zmask) - R.col_lo < R.col_w) << u;
+            }
+        }
+        hit &= box;
+        if (!__ballot(hit != 0)) continue;
+        uint32_t sel = 0;             /* bit u: ... of the wanted hours and group */
+#pragma unroll
+        for (int u = 0; u < U; u++)
+            if ((hit >> u) & 1u)
+                sel |= (uint32_t)hms_raster_in(a, a.buckets.keys[(k[u] >> a.cb) & a.buckets.mask]) << u;
+        if (!__ballot(sel != 0)) continue;
+        uint64_t cn[U];
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const uint64_t i = c0 + (uint64_t)u * 256 + tid;
+            cn[u] = (sel >> u) & 1u ? a.counts[i] : 0ull;
+        }
+        for (int r = 0; r < a.ntiles; r++) {
+            const HmsRasterRect R = a.rects[r];
+            const uint32_t zmask = (1u << R.z) - 1u;
+            unsigned long long* g = a.grid + (uint64_t)r * WW;
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+                const uint64_t d = (k[u] & cmask) - R.id_lo;
+                const uint32_t c = ((uint32_t)d & zmask) - R.col_lo;
+                if (((sel >> u) & 1u) && d < R.span && c < R.col_w)
+                    atomicAdd(&g[((uint32_t)(d >> R.z) + R.y0) * a.W + c + R.x0], (unsigned long long)cn[u]);
+            }
+        }
+    }
+}
+
 /* old-table bucket key of a log cell when it outlives the cut (undated cells
  * have no time and always do), or ~0 */
 __device__ __forceinline__ uint64_t hms_survivor_key(const HmsExpireArgs& a, uint64_t k)
@@ -947,6 +1026,12 @@ void hm_launch_stream_view(hipStream_t s, const HmsViewArgs& a)
 {
     const uint64_t chunks = (a.n + 256 * HMS_VW_U - 1) / (256 * HMS_VW_U);
     if (a.n) hipLaunchKernelGGL(k_stream_view, dim3((unsigned)(chunks < 2048 ? chunks : 2048)), dim3(256), 0, s, a);
+}
+
+void hm_launch_stream_raster(hipStream_t s, const HmsRasterArgs& a)
+{
+    const uint64_t chunks = (a.n + 256 * HMS_VW_U - 1) / (256 * HMS_VW_U);
+    if (a.n) hipLaunchKernelGGL(k_stream_raster, dim3((unsigned)(chunks < 2048 ? chunks : 2048)), dim3(256), 0, s, a);
 }
 
 void hm_launch_stream_expire(hipStream_t s, const HmsExpireArgs& a)

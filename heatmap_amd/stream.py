@@ -20,6 +20,10 @@ label is a device rollup of the hour buckets:
                                tile_rows(tiles, hours, label, user) the rows of
                                the heatmap tiles on screen (hm_stream_view: one
                                pass over the log's keys)
+  tile_raster(tiles, hours, user)  the tiles as dense count grids with a halo
+                               (hm_stream_raster: the same filter pass, no
+                               merge), and tile_images(...) the same blurred,
+                               scaled and coloured into RGBA (heatmap_amd.raster)
   expire(before_hour)          retention: the cells of hours < before_hour
                                leave the stream, their buckets are freed
   snapshot() / save(path)      the whole state as arrays (hm_stream_export: one
@@ -54,6 +58,7 @@ import numpy as np
 
 from . import _lib, device
 from . import heatmap as _hm
+from . import raster as _raster
 
 ALLTIME = -1
 EACH_HOUR = -2
@@ -133,6 +138,32 @@ def tile_rects(tiles, d: int):
     """The detail-zoom rectangle (zoom, row_lo, row_hi, col_lo, col_hi) of each
     heatmap row tile (tz, tr, tc): its 2^d x 2^d bins at zoom tz + d."""
     return [(tz + d, tr << d, (tr + 1) << d, tc << d, (tc + 1) << d) for tz, tr, tc in tiles]
+
+
+def _raster_args(zmin: int, zmax: int, index: dict, tiles, hours, user, bins_log2, halo):
+    """Validated (tiles, hour_lo, hour_hi, group word or None, bins_log2, halo)
+    of StreamingHeatmap.tile_raster on a stream of zooms zmin..zmax whose group
+    labels are `index` (label -> id).  The group word is HM_VIEW_MERGED for
+    user = None, the label's id, or None for a label the stream has never seen
+    (no cell: zero grids).  Pure: needs no device."""
+    tiles, b, h = _raster.check_tiles(tiles, bins_log2, halo, zmin, zmax)
+    if hours is None:
+        lo = hi = _lib.HM_STREAM_ALLTIME
+    else:
+        lo, hi = int(hours[0]), int(hours[1])
+        if hi <= lo:
+            raise ValueError("a window needs hour_lo < hour_hi (got %d, %d)" % (lo, hi))
+    if user is None:
+        gw = _lib.HM_VIEW_MERGED
+    elif user == "all":
+        raise ValueError("a raster counts points: user='all' (the reference's level-weighted 'all' bins) is a "
+                         "property of the row format; use tile_rows(..., user='all'), or user=None for every "
+                         "kept point")
+    elif not isinstance(user, str):
+        raise ValueError("user must be None or a group label (got %r)" % (user,))
+    else:
+        gw = index.get(user)
+    return tiles, lo, hi, gw, b, h
 
 
 def _cells_subset(cells: "_hm.Cells", m: np.ndarray) -> "_hm.Cells":
@@ -702,6 +733,40 @@ class StreamingHeatmap:
     def tile_table(self, tiles, hours=None, label=None, user=None, max_zoom_level=None, delta=None):
         """The same rows as a pyarrow Table(id, heatmap JSON)."""
         return _hm.cells_to_table(self.tile_cells(tiles, hours, label, user, max_zoom_level, delta))
+
+    def tile_raster(self, tiles, hours=None, user=None, bins_log2=5, halo=0):
+        """int64 CUDA tensor [T, W, W], W = 2^bins_log2 + 2 halo: the point
+        counts of the tiles [(tz, tr, tc)] as dense grids of zoom tz +
+        bins_log2 bins, each with a halo of its neighbours' bins, of hours =
+        None (every kept point) or (lo, hi), for every group merged (user =
+        None) or the group label `user` (an unknown label: zero grids).
+        hm_stream_raster: one filter pass over the log, no merge; the
+        out-of-square side records are never drawn."""
+        torch = self._torch
+        self.ctx.bind_stream()
+        tiles, lo, hi, gw, b, h = _raster_args(self.zmin, self.zmax, self._index, tiles, hours, user, bins_log2, halo)
+        w = (1 << b) + 2 * h
+        dev = "cuda:%d" % self.device_index
+        if gw is None:
+            return torch.zeros((len(tiles), w, w), dtype=torch.int64, device=dev)
+        grid = torch.empty((len(tiles), w, w), dtype=torch.int64, device=dev)
+        for j in range(0, len(tiles), _lib.HM_RASTER_MAX_TILES):
+            part = tiles[j:j + _lib.HM_RASTER_MAX_TILES]
+            rc = self.ctx.L.hm_stream_raster(self.ptr, lo, hi, gw, _raster._tile_array(part), len(part), b, h,
+                                             device._ptr(grid[j:j + len(part)]))
+            if rc != _lib.HM_OK:
+                _lib.raise_for(rc)
+        return grid
+
+    def tile_images(self, tiles, hours=None, user=None, bins_log2=8, radius=2, scale="log", vmax=None, ramp="heat"):
+        """uint8 CUDA tensor [T, S, S, 4], S = 2^bins_log2: the tiles as RGBA
+        images -- tile_raster with halo = radius, then raster.render (binomial
+        blur of `radius`, 'log' or 'linear' levels against vmax, or the
+        call's own maximum, coloured through ramp).  raster.png_bytes turns
+        one into a PNG."""
+        _raster.check_render(bins_log2, radius, radius, scale, vmax)
+        grid = self.tile_raster(tiles, hours, user, bins_log2, halo=radius)
+        return _raster.render(grid, bins_log2, radius, radius, scale, vmax, ramp)[0]
 
     def expire(self, before_hour: int):
         """Retention: drop the cells of every hour < before_hour (undated

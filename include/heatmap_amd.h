@@ -96,7 +96,8 @@ extern "C" {
 #define HM_E_CAPACITY 17 /* output arrays too small; *n_out holds the size needed */
 #define HM_E_HIP 18      /* HIP runtime error (no device, launch failure) */
 #define HM_E_NOMEM 19    /* device allocation failed */
-#define HM_E_WIDE 20     /* hm_cells_route with u32 counts: a count >= 2^32 (outputs complete otherwise) */
+#define HM_E_WIDE 20     /* hm_cells_route with u32 counts: a count >= 2^32 (outputs complete otherwise);
+                            hm_raster_render: a bin >= 2^(56 - 4 radius) (outputs untouched) */
 
 /* Output cell key of hm_count: zoom in bits 58..63, row in 29..57, col in 0..28.
  * Sorting keys sorts by (zoom, row, col). */
@@ -369,6 +370,70 @@ int hm_stream_export(hm_stream* s, uint64_t* keys_out, uint64_t* counts_out, uin
 int hm_stream_import(hm_stream* s, const uint64_t* keys, const uint64_t* counts, const uint32_t* groups,
                      const uint32_t* hours, int64_t n, int flags);
 int hm_stream_destroy(hm_stream* s);
+
+/* Rasters: what a tile server sends.  A view lists sparse (key, count) cells
+ * and pays a merge to make them distinct; a raster adds the same cells into
+ * dense grids, where equal cells of different hours and groups simply meet in
+ * one bin, so it needs no merge and no emit.
+ *   Layout.  S = 2^bins_log2, H = halo, W = S + 2H.  grid_out is device
+ *   u64[ntiles][W][W]; tile t = (tz, tr, tc) (tiles: host int64[3 * ntiles])
+ *   holds the bins of zoom tz + bins_log2: element [t][y][x] is the sum of the
+ *   selected cells at row (tr << bins_log2) - H + y, column (tc << bins_log2)
+ *   - H + x.  Bins outside [0, 2^z)^2 are 0 (no wrap at the date line).  The
+ *   call zeroes the grid itself.  Tiles may repeat and be of different zooms;
+ *   every listed tile has its own grid, and a cell inside the haloed squares
+ *   of several tiles is added to each.
+ *   hm_stream_raster  from the resident log, in one filter pass: hours and
+ *                     group as hm_stream_view ([hour_lo, hour_hi) clamped, or
+ *                     the HM_STREAM_ALLTIME pair: undated cells included;
+ *                     group = HM_VIEW_MERGED or one group id 0 .. 0xFFFFFFFE).
+ *                     HM_E_ARG: ntiles outside 1 .. HM_RASTER_MAX_TILES,
+ *                     bins_log2 outside 0 .. HM_RASTER_MAX_BINS_LOG2, halo
+ *                     outside 0 .. HM_RASTER_MAX_HALO, tz < 0, tr or tc outside
+ *                     [0, 2^tz), tz + bins_log2 outside [zmin, zmax], a null
+ *                     pointer, HM_VIEW_EACH, hour_hi <= hour_lo other than the
+ *                     alltime pair; grid_out is then untouched.  An empty
+ *                     selection is HM_OK with an all-zero grid.  The log is
+ *                     left exactly as it is; asynchronous.
+ *   hm_cells_raster   the same from n cells in hm_count's layout (hm_count,
+ *                     rollup, window or view output): equal keys add; tz +
+ *                     bins_log2 in 0 .. HM_MAX_ZOOM; cells of other zooms,
+ *                     outside every haloed square or outside [0, 2^z)^2 are
+ *                     skipped.  n = 0 is HM_OK with a zero grid.  Asynchronous.
+ *   hm_raster_render  blur, normalise and colour the grids into RGBA8, in
+ *                     integer arithmetic throughout (bit-exact by definition):
+ *                     w[k] = C(2R, k), R = radius, 0 <= R <= halo;
+ *                     B[y][x] = sum_i sum_j w[i] w[j] g[H + y - R + i][H + x - R + j]
+ *                     for y, x in [0, S): the blurred count in units of 2^-4R,
+ *                     never divided, so a lone point never disappears, and a
+ *                     tile rendered alone is seamless with its neighbours.
+ *                     Needs max g < 2^(56 - 4R) over the haloed grids (B * 255
+ *                     fits u64): HM_E_WIDE otherwise, rgba_out and levels_out
+ *                     untouched; a vmax >= 2^(56 - 4R) is HM_E_ARG.  Scale unit
+ *                     vs = vmax << 4R for vmax > 0 (a fixed scale: tiles agree
+ *                     across calls), else the maximum of B over the interiors
+ *                     of all tiles of the call; *vmax_used (host, may be NULL)
+ *                     receives vs.  level = 0 where B == 0 or vs == 0, else
+ *                     HM_SCALE_LINEAR: min(255, max(1, B * 255 / vs));
+ *                     HM_SCALE_LOG: min(255, max(1, Q(B) * 255 / max(1, Q(vs)))),
+ *                     Q(v) = q(v + 2^4R) - 256 * 4R, q(u) = 256 e + ((u << (63 -
+ *                     e)) >> 55 & 255), e = floor(log2 u): a piecewise-linear
+ *                     log2(1 + count) with 8 fractional bits.  Pixel = the four
+ *                     bytes of lut[level] (device u32[256], bytes R, G, B, A);
+ *                     rgba_out: device u8[ntiles][S][S][4], 4-byte aligned;
+ *                     levels_out: device u8[ntiles][S][S] or NULL.  Waits once. */
+#define HM_RASTER_MAX_TILES 64
+#define HM_RASTER_MAX_BINS_LOG2 8     /* 256 x 256 bins per tile */
+#define HM_RASTER_MAX_HALO 8
+#define HM_SCALE_LINEAR 0
+#define HM_SCALE_LOG 1
+int hm_stream_raster(hm_stream* s, int64_t hour_lo, int64_t hour_hi, int64_t group,
+                     const int64_t* tiles, int ntiles, int bins_log2, int halo, uint64_t* grid_out);
+int hm_cells_raster(hm_ctx* ctx, const uint64_t* keys, const uint64_t* counts, int64_t n,
+                    const int64_t* tiles, int ntiles, int bins_log2, int halo, uint64_t* grid_out);
+int hm_raster_render(hm_ctx* ctx, const uint64_t* grid, int ntiles, int bins_log2, int halo, int radius,
+                     int scale, uint64_t vmax, const uint32_t* lut, uint8_t* rgba_out, uint8_t* levels_out,
+                     uint64_t* vmax_used);
 
 /* Multi-GPU exchange of hm_count cells (one process per GPU; the collectives
  * are RCCL calls made by the caller, heatmap_amd/multigpu.py).  They replace

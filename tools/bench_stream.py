@@ -52,6 +52,21 @@ over the same log) and "read_stream_GBps".  --readd-only times the re-adding
 alone (nothing newer than hm_stream_window is needed, so a checkout of the
 parent commit can run it); --parent-json FILE puts that run's "readd_ms" into
 this one's result as "parent_readd_ms".
+
+    python tools/bench_stream.py --retain 24 --batches 30 --warmup 0 --raster --out profiles/stream_raster.json
+
+--raster: on the steady retained log, tile rasters (hm_stream_raster) and
+rendered tiles (hm_raster_render) against the view (hm_stream_view) of the same
+haloed rectangles, over the same hours, interleaved in one process, 15
+repetitions each: (a) one heatmap tile, the 32 x 32 bins of zoom 13 around the
+heaviest zoom-13 cell; (b) a 4 x 3-tile screen of 256 x 256-bin tiles of zoom
+18 around the heaviest zoom-18 cell, halo = radius = 2.  Host ms around the C
+call plus a synchronise (and the device ms between two events around the
+raster), median and range; "check": every grid equals the view's cells
+densified in numpy.  --view-only times the views alone (nothing newer than
+hm_stream_view is needed, so a checkout of the parent commit can run it);
+--parent-json FILE puts that run's view times into this one's result as
+"parent_view_ms".
 """
 import argparse
 import json
@@ -166,6 +181,113 @@ def view_bench(s, a, lo, hi):
         out["parent_window_note"] = ("this script with --window-only run by a checkout of the parent commit (its "
                                      "library and package) on the same seeded log, in the same session")
         assert pj["view"]["window_cells"] == n and pj["view"]["log_cells"] == out["log_cells"]
+    return out
+
+
+def _ev_ms(f):
+    """device ms between two events around f() (the launches' own time, without the host's)"""
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    f()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1)
+
+
+def _densify(hk, hc, tiles, b, h):
+    """numpy: cells (hm_count keys, counts) added into the haloed grids of tiles"""
+    import numpy as np
+
+    w = (1 << b) + 2 * h
+    z, r, c = hk >> 58, (hk >> 29) & 0x1FFFFFFF, hk & 0x1FFFFFFF
+    grid = np.zeros((len(tiles), w, w), dtype=np.int64)
+    for t, (tz, tr, tc) in enumerate(tiles):
+        y, x = r - ((tr << b) - h), c - ((tc << b) - h)
+        m = (z == tz + b) & (y >= 0) & (y < w) & (x >= 0) & (x < w)
+        np.add.at(grid[t], (y[m], x[m]), hc[m])
+    return grid
+
+
+def raster_bench(s, a, lo, hi):
+    """--raster (module docstring) on the stream as it stands"""
+    import ctypes
+
+    if not a.view_only:     # the views alone need nothing newer than hm_stream_view
+        from heatmap_amd import _lib, raster
+
+    n, keys, counts, _ = s.window_device(lo, hi)
+    k, cnt = keys[:n], counts[:n]
+    out = {"hours": [lo, hi], "reps": VIEW_REPS, "log_cells": s.cells()[0], "window_cells": n,
+           "timing": "host ms around the call plus one synchronise (raster_dev_ms: device ms between two events "
+                     "around the same call); raster, render and view interleaved"}
+    heavy = {}
+    for z in (13, 18):
+        m = (k >> 58) == z
+        heavy[z] = int(k[torch.argmax(torch.where(m, cnt, torch.full_like(cnt, -1)))].item())
+    del keys, counts, k, cnt
+    r13, c13 = (heavy[13] >> 29) & 0x1FFFFFFF, heavy[13] & 0x1FFFFFFF
+    r18, c18 = (heavy[18] >> 29) & 0x1FFFFFFF, heavy[18] & 0x1FFFFFFF
+    tr, tc = (r18 >> 8) - 1, (c18 >> 8) - 1
+    cases = {"a_one_tile_z13_32x32": ([(8, r13 >> 5, c13 >> 5)], 5, 0, None),
+             "b_screen_4x3_tiles_256x256_r2": ([(10, tr + i, tc + j) for i in range(3) for j in range(4)], 8, 2, 2)}
+    L, ok = s.ctx.L, True
+    for name, (tiles, b, h, radius) in cases.items():
+        w, side = (1 << b) + 2 * h, 1 << b
+        rects = [(tz + b, (y << b) - h, (y << b) - h + w, (x << b) - h, (x << b) - h + w) for tz, y, x in tiles]
+        grid = torch.empty((len(tiles), w, w), dtype=torch.int64, device="cuda")
+        rgba = torch.empty((len(tiles), side, side, 4), dtype=torch.uint8, device="cuda")
+        used = ctypes.c_uint64(0)
+        if not a.view_only:
+            ta = raster._tile_array(tiles)
+            lut = raster._lut("heat", torch, grid.device)
+
+        def do_raster():
+            rc = L.hm_stream_raster(s.ptr, lo, hi, _lib.HM_VIEW_MERGED, ta, len(tiles), b, h, grid.data_ptr())
+            assert rc == 0, rc
+
+        def do_render():
+            rc = L.hm_raster_render(s.ctx.ptr, grid.data_ptr(), len(tiles), b, h, radius, _lib.HM_SCALE_LOG, 0,
+                                    lut.data_ptr(), rgba.data_ptr(), None, ctypes.byref(used))
+            assert rc == 0, rc
+
+        t_view, t_ras, t_dev, t_ren = [], [], [], []
+        s.view_device(rects, (lo, hi))              # warm: code objects, the capacity memo
+        if not a.view_only:
+            do_raster()
+            if radius is not None:
+                do_render()
+        for _ in range(VIEW_REPS):
+            t_view.append(_ms(lambda: s.view_device(rects, (lo, hi)))[0])
+            if a.view_only:
+                continue
+            t_ras.append(_ms(do_raster)[0])
+            t_dev.append(_ev_ms(do_raster))
+            if radius is not None:
+                t_ren.append(_ms(do_render)[0])
+        nv, vk, vc, _ = s.view_device(rects, (lo, hi))
+        res = {"tiles": [list(t) for t in tiles], "bins_log2": b, "halo": h, "view_rects": [list(q) for q in rects],
+               "view_cells_out": nv, "view_ms": _stats(t_view)}
+        if not a.view_only:
+            do_raster()
+            want = _densify(vk[:nv].cpu().numpy(), vc[:nv].cpu().numpy(), tiles, b, h)
+            same = nv > 0 and bool((grid.cpu().numpy() == want).all())
+            ok &= same
+            res.update({"raster_ms": _stats(t_ras), "raster_dev_ms": _stats(t_dev), "grid_sum": int(grid.sum()),
+                        "grid_equals_densified_view": same})
+            if radius is not None:
+                res.update({"radius": radius, "render_ms": _stats(t_ren), "vmax_used": used.value,
+                            "pixels_drawn": int((rgba[..., 3] != 0).sum())})
+        out[name] = res
+    if not a.view_only:
+        out["check"] = "ok" if ok else "FAIL"
+    if a.parent_json:
+        pj = json.load(open(a.parent_json))["raster"]
+        assert pj["window_cells"] == n and pj["log_cells"] == out["log_cells"]
+        for name in cases:
+            assert pj[name]["view_cells_out"] == out[name]["view_cells_out"]
+            out[name]["parent_view_ms"] = pj[name]["view_ms"]
+        out["parent_view_note"] = ("this script with --raster --view-only run by a checkout of the parent commit (its "
+                                   "library and package) on the same seeded log, in the same session")
     return out
 
 
@@ -308,6 +430,7 @@ def retain(a):
     steady = [x for x in series if x["batch"] > H]
     view = view_bench(s, a, BASE + total - 1 - H, BASE + total) if a.view else None
     snap = snapshot_bench(s, a, lat, lon, list(range(total - 1 - H, total))) if a.snapshot or a.readd_only else None
+    ras = raster_bench(s, a, BASE + total - 1 - H, BASE + total) if a.raster else None
     result = json.dumps({
         "metric": "stream under retention: expire(newest - H) and window(newest - H, newest + 1) per one-hour batch",
         "retain_hours": H, "batch_points": n, "batches": a.batches, "warmup": a.warmup, "zooms": [a.zmin, a.zmax],
@@ -322,6 +445,7 @@ def retain(a):
         if steady else None,
         "view": view,
         "snapshot": snap,
+        "raster": ras,
         "series": series,
         "data": "synthetic (heatmap_amd.synth, generated on device, resident in HBM)"})
     print(result)
@@ -349,11 +473,16 @@ def main():
     ap.add_argument("--window-only", action="store_true", help="with --view: time the window alone")
     ap.add_argument("--snapshot", action="store_true",
                     help="with --retain: export, import and save/load of the steady log (module docstring)")
+    ap.add_argument("--raster", action="store_true",
+                    help="with --retain: tile rasters and rendered tiles vs views of the same rectangles (module "
+                         "docstring)")
+    ap.add_argument("--view-only", action="store_true", help="with --raster: time the views alone")
     ap.add_argument("--readd-only", action="store_true",
                     help="with --retain: time only the re-adding of the retained batches to a fresh stream")
     ap.add_argument("--parent-json", default=None, metavar="FILE",
                     help="with --view: a --window-only result of the parent commit, kept as parent_window; with "
-                         "--snapshot: its --readd-only result, kept as parent_readd_ms")
+                         "--snapshot: its --readd-only result, kept as parent_readd_ms; with --raster: its "
+                         "--view-only result, kept as parent_view_ms")
     ap.add_argument("--out", default=None, metavar="FILE", help="with --retain: also write the JSON line to FILE")
     a = ap.parse_args()
     if a.retain > 0:
