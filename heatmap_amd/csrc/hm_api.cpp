@@ -7,6 +7,8 @@
  *   -> k_aggregate (zooms Z..zb+1) -> k_pool for l = L..1 (zooms zb..0).
  * The host reads back two or three scalars per level (bucket and work-item
  * counts) to size the next grid; everything else stays on the device.
+ * The driver is CountCall: run() calls its phases in that order, and LevelOut
+ * is what one level hands to the next.
  */
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -636,7 +638,7 @@ static int gen_count(hm_ctx* ctx, const int64_t* row, const int64_t* col, const 
     return HM_OK;
 }
 
-#define HM_FALLBACK (-1)   /* count_impl: the pipeline's dense child space is too large */
+#define HM_FALLBACK (-1)   /* CountCall: the pipeline's dense child space is too large */
 
 /* hm_count for data too sparse for the pipeline's dense per-level child
  * arrays (e.g. uniform clouds at zoom 21): every kept point through the
@@ -718,12 +720,166 @@ static void spread_replan(const uint32_t* h, int F, double npts, int zb, int* zs
     *L = l;
 }
 
-static int count_impl(hm_ctx* ctx, const double* lat, const double* lon, const int64_t* rows, const int64_t* cols,
-                      const uint8_t* keep, int64_t n, int zmin, int zmax, uint64_t* keys_out, uint64_t* counts_out,
-                      int64_t capacity, int64_t* n_out, int64_t* xcells_out, int64_t xcapacity, int64_t* nx_out)
+/* ------------------------------------------------------------------------ */
+/* the count pipeline's host driver.  One CountCall per attempt of hm_count / */
+/* hm_count_tiles; run() is the driver: plan, level 1, levels 2..L,           */
+/* aggregate, pool, finish.  The phases return the status code.               */
+/* ------------------------------------------------------------------------ */
+namespace {
+
+/* What level l hands to level l + 1 (the last level: to the aggregation).
+ * Beside it the next level reads only B[l] and lv[l].items, and the hot-tile
+ * state below. */
+struct LevelOut {
+    void* keys = nullptr;                          /* the level's output keys: u32, u16 from the last level */
+    int slot_k = 0;                                /* ping-pong A/B: which of B_KEYS_*, B_FLAT_*, B_EXCL_* the
+                                                    * next level writes (the other holds keys and runs) */
+    HmRuns runs = {nullptr, nullptr};              /* flat child-ordered runs and their key prefix */
+    const uint32_t* parent_item_begin = nullptr;   /* B_l's work-item prefix */
+    const uint64_t* parent_coord = nullptr;        /* B_l's tiles */
+    uint32_t nparents = 1;                         /* |B_l| (the root below level 1) */
+    uint64_t level_keys = 0;                       /* keys entering level l + 1 (global positions) */
+    uint32_t* seg = nullptr;                       /* B_l's items' run tables (k_partition_fr): level 1's when
+                                                    * L > 1, a child-contiguous level's, else null */
+};
+
+/* level 1's kernel arguments and sizes, shared by its pieces */
+struct Level1Work {
+    HmPart1Args a;                   /* holds fill, l1slot and redo_idx */
+    uint32_t *rbase, *rcap;          /* the regions' bases and sizes */
+    uint8_t* smask;
+    HmL1Args ba;                     /* k_level1_buckets */
+    int F;                           /* digits of the level */
+    uint32_t* hist;                  /* sampled digit histogram */
+    int64_t *redo_rows, *redo_cols;  /* the deferred points, resolved (lat/lon input) */
+    uint64_t stride;                 /* points per sample */
+    uint64_t total_cap;              /* key positions of the regions */
+    void* kout;
+};
+
+/* one level >= 2: what level_begin chooses and the buffers its pieces share */
+struct LevelWork {
+    int restbits;
+    bool contig;          /* child-contiguous level (HM_PN_CONTIG) */
+    bool hot3;            /* hot tiles in a 3-level plan, joining at the last level */
+    int sb;               /* run-counter shard bits */
+    uint64_t l1_total;    /* where level 1's key positions end */
+    void* kout;
+    uint2* runs_sh;
+    uint32_t* nruns;
+    uint32_t* rs_big;
+    HmRsArgs ra;          /* the run scan's arrays (compact reads nr, runbase, nkeys, keybase, vals) */
+    uint64_t* prefix;
+};
+
+struct CountCall {
+    /* ---- arguments ---- */
+    hm_ctx* ctx;
+    const double* lat;
+    const double* lon;
+    const int64_t* rows;
+    const int64_t* cols;
+    const uint8_t* keep;
+    int64_t n;
+    int zmin, Z;
+    uint64_t* keys_out;
+    uint64_t* counts_out;
+    int64_t capacity;
+    int64_t* n_out;
+    int64_t* xcells_out;
+    int64_t xcapacity;
+    int64_t* nx_out;
+
+    /* ---- the plan (plan(); L and zs[1..] revised once, at the end of level 1) ---- */
+    hipStream_t s = nullptr;
+    int zb = 0;                 /* bucket zoom of the last level */
+    int zs[HM_MAX_LEVELS];      /* child zoom of each level */
+    int L = 0;
+    uint32_t ta = HM_TA;        /* keys per aggregation work item */
+    bool timing = false;        /* stage events recorded */
+    uint32_t tiles_in = 0;      /* HM_T1-point input tiles */
+    bool from_tiles = false;    /* hm_count_tiles */
+    uint64_t redo_cap = 0;      /* capacity of k_redo's list */
+    bool spread = false;        /* levels 2.. take fewer zooms (spread_replan) */
+
+    /* ---- level l -> level l + 1 ---- */
+    LevelOut hand;
+
+    /* ---- hot tiles ---- */
+    bool hot_on = false;        /* hot tiles sampled and looked up by level 1 */
+    bool hot_mid = false;       /* ... at zs[1] of a 3-level plan (they skip level 2 only) */
+    int hz = 0;                 /* zoom of the hot tiles: the bucket zoom of level 2 */
+    uint32_t nhot = 0;          /* hot tiles found */
+    uint64_t l2_elems = 0;      /* mid-level hot tiles: level 2's key array (elements) */
+    HmHotRunArgs hr = {};       /* hot tiles as level-2 children */
+
+    /* ---- what aggregate(), pool() and finish() read ---- */
+    Level lv[HM_MAX_LEVELS];
+    HmBuckets B[HM_MAX_LEVELS] = {};
+    unsigned long long* totals[HM_MAX_LEVELS + 1];
+    uint32_t nslots = 0;        /* the last level's multi-item buckets (merge slots) */
+    int32_t* slots = nullptr;
+    uint32_t* slot_bucket = nullptr;
+    HmExotic xl = {};           /* kept points outside [0, 2^Z)^2 */
+    uint64_t nx = 0;            /* ... their number */
+    HmOut o;
+
+    /* ---- hm_last_stats ---- */
+    int l1_reruns = 0;          /* level-1 re-runs after a region overflow */
+    int npart = 0;              /* level >= 2 partition launches timed (ev[5..]) */
+    int nev = 0;                /* stage-boundary events recorded (ev[0..4]) */
+
+    /* digit slots: F cold digits, hot tile h at HM_MAX_F1 + h */
+    static constexpr int FS = HM_D1 * HM_L1_SHARDS;
+    /* a level's totals (runs, keys, count << 32 | items): they come back with the state */
+    uint64_t* ltot() const { return (uint64_t*)(ctx->state + ST_LTOT); }
+
+    int run();
+    int plan();
+    int begin_level(int l);
+    int bucket_arrays(int l, uint64_t cap, HmCompactOut& out);
+    int publish(int l, const HmCompactOut& out, HmRuns runs, void* keys, uint64_t level_keys, int seg_slot);
+    int level1();
+    int level1_setup(Level1Work& w);
+    int level1_size(Level1Work& w);
+    int level1_bucket_args(Level1Work& w);
+    int level1_resize(Level1Work& w);
+    int level1_redo(Level1Work& w);
+    int level1_buckets(Level1Work& w);
+    int level1_run(Level1Work& w);
+    int level1_finish(Level1Work& w);
+    int level(int l);
+    int level_begin(int l, LevelWork& w);
+    int level_partition(int l, LevelWork& w);
+    int level_runscan(int l, LevelWork& w);
+    int level_compact(int l, LevelWork& w);
+    int aggregate();
+    int pool();
+    int finish();
+};
+
+int CountCall::run()
 {
-    if (!ctx || !n_out || !nx_out || n < 0 || n >= (int64_t)0xFFFFFFF0ll || zmin < 0 || zmax < zmin ||
-        zmax > HM_COUNT_MAX_ZOOM || capacity < 0 || (capacity > 0 && (!keys_out || !counts_out)) || xcapacity < 0 ||
+    int st;
+    if ((st = plan())) return st;
+    if ((st = level1())) return st;
+    for (int l = 1; l < L; l++)
+        if ((st = level(l))) return st;
+    if (timing) HIPCHK(hipEventRecord(ctx->ev[nev], s));
+    nev++;
+    if ((st = aggregate())) return st;
+    if (timing) HIPCHK(hipEventRecord(ctx->ev[nev], s));
+    nev++;
+    if ((st = pool())) return st;
+    if (timing) HIPCHK(hipEventRecord(ctx->ev[nev], s));
+    nev++;
+    return finish();
+}
+
+int CountCall::plan()
+{
+    if (!ctx || !n_out || !nx_out || n < 0 || n >= (int64_t)0xFFFFFFF0ll || zmin < 0 || Z < zmin ||
+        Z > HM_COUNT_MAX_ZOOM || capacity < 0 || (capacity > 0 && (!keys_out || !counts_out)) || xcapacity < 0 ||
         (xcapacity > 0 && !xcells_out))
         return HM_E_ARG;
     *n_out = 0;
@@ -732,11 +888,9 @@ static int count_impl(hm_ctx* ctx, const double* lat, const double* lon, const i
      * that fails after it, then count_fallback, leaves the keys un-keyed) */
     ctx->tail_done = 0;
     HIPCHK(hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
-    const int Z = zmax;
-    const int zb = Z > HM_AG_LG ? Z - HM_AG_LG : 0;
-    int zs[HM_MAX_LEVELS];
-    int L = 0;
+    s = ctx->stream;
+    zb = Z > HM_AG_LG ? Z - HM_AG_LG : 0;
+    hz = zb;
     {
         int z = zb < HM_Z1 ? zb : HM_Z1;
         zs[L++] = z;
@@ -748,25 +902,13 @@ static int count_impl(hm_ctx* ctx, const double* lat, const double* lon, const i
     }
     /* key bits after level l: 2*(Z - zs[l]); must fit u32 (level 1 output) */
     if (2 * (Z - zs[0]) > 32) return HM_E_ARG;
-    int st = HM_OK;
-    /* the call's state words and level 1's zeroed buffers: one fill dispatch,
-     * launched before level 1's sampling */
-    HmFill f1;
-    memset(&f1, 0, sizeof(f1));
-    hm_fill_add(f1, ctx->state + 1, 0, (ST_COUNT - 1) * sizeof(unsigned long long));
-    hm_fill_add(f1, ctx->state + ST_ERR, 0xFF, sizeof(unsigned long long));
-    static_assert(ST_ERR == 0, "error word first");
-
-    hipEvent_t* ev = ctx->ev;
-    int nev = 0;
     /* stage timings (hm_last_stats) for calls of >= 2^24 points: each event
      * record is an API call, and small calls (stream batches) are bound by
      * the host's issue rate */
-    const bool timing = n >= (1ll << 24) && ctx->stage_timing;
+    timing = n >= (1ll << 24) && ctx->stage_timing;
     /* keys per aggregation work item: HM_TA, halved (down to HM_TA_MIN, 16K)
      * until the call has >= HM_TA_ITEMS (128) items' worth of points -- a
      * 1e7-point call otherwise runs ~40 items on 256 CUs */
-    uint32_t ta = HM_TA;
     while (ta > ctx->ta_min && (uint64_t)n < (uint64_t)ta * ctx->ta_items) ta >>= 1;
     for (int i = 0; i < 9; i++) ctx->stage_us[i] = 0;
     ctx->stage_us[8] = (double)ta;          /* hm_last_stats: keys per aggregation work item */
@@ -774,718 +916,770 @@ static int count_impl(hm_ctx* ctx, const double* lat, const double* lon, const i
 
     /* level 1 reads the input in HM_T1-point tiles; points the fast path
      * defers (lat/lon input only) go to k_redo, at most redo_cap of them */
-    const uint32_t tiles_in = (uint32_t)((n + HM_T1 - 1) / HM_T1);
-    const bool from_tiles = rows != nullptr;
-    uint64_t redo_cap = from_tiles ? 0 : std::max<uint64_t>(1u << 20, (uint64_t)n / 256);
+    tiles_in = (uint32_t)((n + HM_T1 - 1) / HM_T1);
+    from_tiles = rows != nullptr;
+    redo_cap = from_tiles ? 0 : std::max<uint64_t>(1u << 20, (uint64_t)n / 256);
     if (redo_cap > (uint64_t)n) redo_cap = (uint64_t)n;
     /* exotic list: first capacity like the redo list's; rebuilt if it overflows */
-    HmExotic xl;
     xl.cap = std::min<uint64_t>((uint64_t)n, std::max<uint64_t>(1u << 20, (uint64_t)n / 256));
     ENSURE(B_X_ROW, xl.cap * 8 + 8, xl.row);
     ENSURE(B_X_COL, xl.cap * 8 + 8, xl.col);
     ENSURE(B_X_IDX, xl.cap * 8 + 8, xl.idx);
     xl.count = ctx->state + ST_XCOUNT;
-    const uint32_t* parent_item_begin = nullptr;
-    const uint64_t* parent_coord = nullptr;
-    uint32_t nparents = 1;
+    return HM_OK;
+}
 
-    Level lv[HM_MAX_LEVELS];
-    HmBuckets B[HM_MAX_LEVELS];
-    memset(B, 0, sizeof(B));
-    void* keys_cur = nullptr;
-    HmRuns runs_cur = {nullptr, nullptr};
-    int slot_k = 0; /* ping-pong A/B */
-    uint32_t nslots = 0;
-    int32_t* slots = nullptr;
-    uint32_t* slot_bucket = nullptr;
-    uint64_t level_keys = 0;    /* keys entering level l >= 2 (global positions) */
-    uint64_t nx = 0;            /* kept points outside [0, 2^Z)^2 */
-    int npart = 0;              /* level >= 2 partition launches timed (ev[5..]) */
+/* level l's descriptor, from the plan as it stands (level 1: before the
+ * replan; levels >= 2: after it) and the buckets the level below published */
+int CountCall::begin_level(int l)
+{
+    Level& V = lv[l];
+    V.zc = zs[l];
+    V.dbits = 2 * (zs[l] - (l ? zs[l - 1] : 0));
+    V.nparents = hand.nparents;
+    V.nchildren = (uint64_t)hand.nparents << V.dbits;
+    V.out16 = (l == L - 1);
+    if (V.nchildren > (uint64_t)HM_SCAN_LIMIT) return HM_FALLBACK;
+    return HM_OK;
+}
 
-    uint32_t* seg1 = nullptr;   /* level-1 items' run tables (k_partition_fr) */
-    uint32_t* seg2 = nullptr;   /* level-2 items' run tables after a child-contiguous level */
-    bool hot_on = false;        /* hot tiles sampled and looked up by level 1 */
-    bool hot_mid = false;       /* ... at zs[1] of a 3-level plan (they skip level 2 only) */
-    int hz = zb;                /* zoom of the hot tiles: the bucket zoom of level 2 */
-    bool spread = false;        /* levels 2.. take fewer zooms (spread_replan) */
-    uint32_t nhot = 0;          /* hot tiles found */
-    uint64_t l2_elems = 0;      /* mid-level hot tiles: level 2's key array (elements) */
-    int l1_reruns = 0;          /* level-1 re-runs after a region overflow */
-    HmHotRunArgs hr;            /* hot tiles as level-2 children */
-    memset(&hr, 0, sizeof(hr));
-    for (int l = 0; l < L; l++) {
-        Level& V = lv[l];
-        V.zc = zs[l];
-        V.dbits = 2 * (zs[l] - (l ? zs[l - 1] : 0));
-        V.nparents = nparents;
-        V.nchildren = (uint64_t)nparents << V.dbits;
-        V.out16 = (l == L - 1);
-        const int restbits = 2 * (Z - zs[l]);
-        if (V.nchildren > (uint64_t)HM_SCAN_LIMIT) return HM_FALLBACK;
-        if (l == 0) {
-            /* ---- level 1: projection + partition into per-digit regions ---- */
-            const int F = 1 << V.dbits;
-            /* digit slots: F cold digits, hot tile h at HM_MAX_F1 + h */
-            const int FS = HM_D1 * HM_L1_SHARDS;
-            uint32_t *fill, *rbase, *rcap, *hist;
-            uint8_t* smask;
-            ENSURE(B_L1_FILL, FS * 4, fill);
-            ENSURE(B_L1_RBASE, FS * 4, rbase);
-            ENSURE(B_L1_RCAP, FS * 4, rcap);
-            ENSURE(B_L1_HIST, HM_D1 * 4, hist);
-            ENSURE(B_L1_SMASK, HM_D1, smask);
-            uint4* l1slot = nullptr;   /* k_l1_fast's slot table (lat/lon input) */
-            if (!from_tiles) ENSURE(B_L1_SLOT, (size_t)FS * sizeof(uint4), l1slot);
-            /* hot tiles are level-2 buckets: zoom zs[1], a dense sample
-             * histogram of <= 4^11 tiles.  In the two-level plan (level 1 at
-             * z1, the last at zb) they skip every partition after level 1; in
-             * a three-level plan (zmax 19-21: z5 -> z11 -> zb) they skip level 2
-             * and join level 3 with the level-2 buckets (HM_HOT_MID) */
-            hot_mid = ctx->hot && ctx->hot_mid && L == 3 && zs[1] <= 11 && zs[0] == HM_Z1 && n > 0 &&
-                      V.dbits == 2 * HM_Z1;
-            hot_on = hot_mid || (ctx->hot && L == 2 && zb <= 11 && zs[0] == HM_Z1 && n > 0 && V.dbits == 2 * HM_Z1);
-            hz = hot_mid ? zs[1] : zb;
-            uint32_t* redo_idx = nullptr;
-            int64_t *redo_rows = nullptr, *redo_cols = nullptr;
-            if (!from_tiles) {
-                ENSURE(B_REDO_IDX, redo_cap * sizeof(uint32_t), redo_idx);
-                ENSURE(B_REDO_ROWS, redo_cap * sizeof(int64_t), redo_rows);
-                ENSURE(B_REDO_COLS, redo_cap * sizeof(int64_t), redo_cols);
-            }
-            HmPart1Args a;
-            memset(&a, 0, sizeof(a));
-            a.lat = lat;
-            a.lon = lon;
-            a.rows_in = rows;
-            a.cols_in = cols;
-            a.keep = keep;
-            a.n = n;
-            a.Z = Z;
-            a.dbits = V.dbits;
-            a.restbits = restbits;
-            a.fill = fill;
-            a.rbase = rbase;
-            a.rcap = rcap;
-            a.smask = smask;
-            a.l1slot = l1slot;
-            a.overflow = ctx->state + ST_OVERFLOW;
-            a.err_word = ctx->state + ST_ERR;
-            a.x = xl;
-            a.slow_count = ctx->state + ST_SLOW;
-            a.redo_idx = redo_idx;
-            a.redo_count = ctx->state + ST_REDO;
-            a.redo_cap = redo_cap;
-            /* region sizes: a sampled digit histogram with a generous margin */
-            /* ~256K samples (1M samples above 2^28 points took 90 us per 1e9-point
-             * count; the regions' 8-sigma margins scale with sqrt(stride)) */
-            /* (2^16 samples below 2^24 points, where the sample pass's ~30 us
-             * is a batch's cost; the regions' slack scales with the stride) */
-            const int slog = n < (1ll << 24) ? std::min(ctx->sample_log2, 16) : ctx->sample_log2;
-            const uint64_t stride = std::max<uint64_t>(1, (uint64_t)n >> slog);
-            hm_fill_add(f1, hist, 0, HM_D1 * 4);
-            hm_fill_add(f1, fill, 0, FS * 4);
-            uint32_t* hot_counts = nullptr;
-            uint32_t* hot_tiles = nullptr;
-            uint32_t* hot_hash = nullptr;
-            uint8_t* hot_parent = nullptr;
-            uint32_t* hot_n = (uint32_t*)(ctx->state + ST_NHOT);
-            if (hot_on) {
-                ENSURE(B_HOT_COUNTS, (4ull << (2 * hz)), hot_counts);
-                ENSURE(B_HOT, (HM_MAX_HOT + HM_HOT_SLOTS + 2 * HM_HOT_CAND + 1) * 4, hot_tiles);
-                ENSURE(B_HOT_PARENT, HM_MAX_F1, hot_parent);
-                hot_hash = hot_tiles + HM_MAX_HOT;
-                hm_fill_add(f1, hot_counts, 0, 4ull << (2 * hz));
-                hm_fill_add(f1, hot_hash + HM_HOT_SLOTS + 2 * HM_HOT_CAND, 0, 4);   /* candidates */
-                hm_fill_add(f1, hot_parent, 0, HM_MAX_F1);
-                a.hot_z = hz;
-                a.hot_bytes = hot_mid ? 4 : 2;
-                a.hot_hash = hot_hash;
-                a.hot_n = hot_n;
-            } else {
-                a.hot_z = -1;
-            }
-            hm_launch_fill(s, f1);
-            f1.k = 0;
-            if (n > 0) hm_launch_sample_digits(s, a, stride, hist, hot_counts);
-            HIPCHK(hipGetLastError());
-            if (hot_on) {
-                hr.tiles = hot_tiles;
-                hr.n = hot_n;
-                hr.zb = hz;
-                hr.z1 = zs[0];
-                hr.fill = fill;
-                hr.rbase = rbase;
-                HmHotArgs ha;
-                ha.counts = hot_counts;
-                ha.zb = hz;
-                ha.z1 = zs[0];
-                const uint64_t m = ((uint64_t)n + stride - 1) / stride;
-                ha.thresh = (uint32_t)std::max<double>(
-                    {1.0, ceil((double)m / ctx->hot_inv_share), ceil(ctx->hot_min_keys / (double)stride)});
-                ha.tiles = hot_tiles;
-                ha.hist = hist;
-                ha.hotparent = hot_parent;
-                ha.n = hot_n;
-                ha.hash = hot_hash;
-                ha.cand = hot_hash + HM_HOT_SLOTS;
-                hm_launch_hot_select(s, ha);
-                HIPCHK(hipGetLastError());
-            }
-            /* pinned host scratch (the overflow retry): caps [FS] | bases [FS] */
-            uint32_t* hc = ctx->host_aux + HM_D1;
-            uint32_t* hb = hc + HM_D1 * HM_L1_SHARDS;
-            /* the region sizes are computed on the device (k_l1_sizes); the key
-             * buffer takes the host's bound of their total: est sums to at
-             * most nn (a hot tile's samples leave its cold digit), at most M
-             * (digit, shard) entries are non-empty, and sum sqrt(e stride) <=
-             * sqrt(M nn stride) (Cauchy-Schwarz) */
-            const double nn = (double)n + (double)(F + (hot_on ? HM_MAX_HOT : 0)) * (double)stride;
-            const double M = F + std::min((double)F, nn / ((double)HM_L1_SHARD_TILES * HM_T1)) * (HM_L1_SHARDS - 1) +
-                             (hot_on ? (double)HM_MAX_HOT * HM_L1_SHARDS : 0.0);
-            double bound = nn * 17.0 / 16.0 + 8.0 * sqrt(M * nn * (double)stride) + M * 2.0 * HM_T1 +
-                           (double)(F + (hot_on ? HM_MAX_HOT : 0)) * HM_L1_ZERO_SAMPLES * (double)stride + 1024.0;
-            hm_launch_l1_sizes(s, hist, F, hot_on ? hot_n : nullptr, stride, rcap, rbase, smask,
-                               ctx->state + ST_L1TOTAL);
-            if (l1slot) hm_launch_l1_slots(s, a);
-            HIPCHK(hipGetLastError());
-            if (bound >= (double)0xFFF00000ull) {
-                /* the bound passes the u32 key positions (n above ~1.5e9):
-                 * read the exact total of the sized regions instead */
-                if ((st = read_state(ctx))) return st;
-                bound = (double)ctx->host_state[ST_L1TOTAL] + 1024.0;
-                if (bound >= (double)0xFFF00000ull) return HM_FALLBACK;   /* key positions are u32 */
-            }
-            /* the non-empty digits are the level's buckets, one run each */
-            HmL1Args ba;
-            memset(&ba, 0, sizeof(ba));
-            const uint64_t cap = (uint64_t)F + 1;
-            ENSURE(B_BK0 + 0, cap * 4, ba.out.nkeys);
-            ENSURE(B_BK0 + 1, cap * 4, ba.out.nruns);
-            ENSURE(B_BK0 + 2, cap * 4, ba.out.rbase);
-            ENSURE(B_BK0 + 3, cap * 4, ba.out.item_begin);
-            ENSURE(B_BK0 + 4, cap * 4, ba.out.digit);
-            ENSURE(B_BK0 + 5, cap * 8, ba.out.coord);
-            ENSURE(B_BK0 + 6, cap * 4, ba.out.keybase);
-            ENSURE(B_FLAT_A, (uint64_t)FS * sizeof(uint2) + 8, ba.runs);
-            ENSURE(B_EXCL_A, (uint64_t)FS * sizeof(uint64_t) + 8, ba.excl);
-            ENSURE(B_CHILD0, 2 * 4, ba.child_begin);
-            uint64_t* tot = (uint64_t*)(ctx->state + ST_LTOT);   /* comes back with the state */
-            ba.F = F;
-            ba.dbits = V.dbits;
-            ba.fill = fill;
-            ba.rbase = rbase;
-            ba.smask = smask;
-            ba.item_keys = (L == 1) ? ta : HM_TN;
-            ba.sparse_max = (L == 1) ? HM_SP_MAX : 0u;
-            ba.total = tot;
-            if (hot_on) {   /* hot parents all zero when no tile turned out hot */
-                uint32_t* d2b;
-                ENSURE(B_D2B, HM_MAX_F1 * 4, d2b);
-                ba.hotparent = hr.tiles ? (const uint8_t*)ctx->bufs[B_HOT_PARENT].p : nullptr;
-                ba.d2b = d2b;
-                hr.d2b = d2b;
-            }
-            if (L == 1) {
-                ENSURE(B_SLOTS, cap * 4, slots);
-                ENSURE(B_SLOTBKT, cap * 4, slot_bucket);
-                ba.slots = slots;
-                ba.nslots = ctx->state + ST_NSLOTS;
-                ba.slot_bucket = slot_bucket;
-            }
-            unsigned long long* down = ctx->host_state + 2 * ST_COUNT;
-            void* kout = nullptr;
-            uint64_t total_cap = (uint64_t)bound;
-            for (int attempt = 0;; attempt++) {
-                if (attempt > 0) {
-                    /* a digit's shards stay consecutive: its keys' logical
-                     * positions are one range (k_level1_buckets) */
-                    total_cap = 0;
-                    for (int d = 0; d < HM_D1; d++)
-                        for (int sh = 0; sh < HM_L1_SHARDS; sh++) {
-                            hb[hm_l1i(d, sh)] = (uint32_t)total_cap;
-                            total_cap += hc[hm_l1i(d, sh)];
-                        }
-                    if (total_cap >= 0xFFF00000ull) return HM_FALLBACK;
-                    HIPCHK(hipMemcpyAsync(rcap, hc, FS * 4, hipMemcpyHostToDevice, s));
-                    HIPCHK(hipMemcpyAsync(rbase, hb, FS * 4, hipMemcpyHostToDevice, s));
-                    if (l1slot) hm_launch_l1_slots(s, a);   /* the table holds the regions' bases and sizes */
-                }
-                ENSURE(slot_k ? B_KEYS_B : B_KEYS_A, (total_cap + 8) * (V.out16 ? 2 : 4), kout);
-                a.keys_out = kout;
-                if (hot_on) {
-                    /* hot keys: straight into level 2's output key array (level 2
-                     * writes the cold keys' positions of it): u16 when that is the
-                     * last level's, u32 for mid-level hot tiles -- whose array
-                     * also holds the child-contiguous cold keys above every
-                     * level-1 position (l2_elems) */
-                    void* kh = nullptr;
-                    if (hot_mid) l2_elems = total_cap + (uint64_t)n + 16;
-                    ENSURE(slot_k ? B_KEYS_A : B_KEYS_B, hot_mid ? l2_elems * 4 : (total_cap + 8) * 2, kh);
-                    a.keys_hot = kh;
-                }
-                if (attempt > 0) {
-                    /* (the first attempt's are zero from the call's fill) */
-                    HIPCHK(hipMemsetAsync(fill, 0, FS * 4, s));
-                    /* ST_XCOUNT .. ST_OVERFLOW (XCOUNT, SLOW, REDO, REDO_OUT, OVERFLOW;
-                     * CURSOR, NSLOTS, XCURSOR are still 0 here) in one memset */
-                    static_assert(ST_XCOUNT == 1 && ST_OVERFLOW == 8 && ST_NHOT > ST_OVERFLOW, "level-1 words");
-                    HIPCHK(hipMemsetAsync(ctx->state + ST_XCOUNT, 0, 8 * 8, s));
-                }
-                if (timing) HIPCHK(hipEventRecord(ev[0], s));
-                hm_launch_part1(s, a, tiles_in, V.out16, from_tiles ? 1 : 0);
-                HIPCHK(hipGetLastError());
-                if (timing) HIPCHK(hipEventRecord(ev[1], s));
-                nev = 2;
-                if (!from_tiles) {
-                    HmRedoArgs ra;
-                    ra.lat = lat;
-                    ra.lon = lon;
-                    ra.keep = keep;
-                    ra.Z = Z;
-                    ra.redo_idx = redo_idx;
-                    ra.redo_count = ctx->state + ST_REDO;
-                    ra.rows_out = redo_rows;
-                    ra.cols_out = redo_cols;
-                    ra.out_count = ctx->state + ST_REDO_OUT;
-                    ra.err_word = ctx->state + ST_ERR;
-                    ra.x = xl;
-                    ra.cap = redo_cap;
-                    hm_launch_redo(s, ra, redo_cap);
-                    HIPCHK(hipGetLastError());
-                }
-                if (!from_tiles) {
-                    /* the deferred points, resolved exactly, as tile input; the
-                     * launch covers the list's capacity and reads its length
-                     * on the device (no host round trip) */
-                    HmPart1Args b = a;
-                    b.lat = nullptr;
-                    b.lon = nullptr;
-                    b.rows_in = redo_rows;
-                    b.cols_in = redo_cols;
-                    b.keep = nullptr;
-                    b.n = (int64_t)redo_cap;
-                    b.n_dev = ctx->state + ST_REDO_OUT;
-                    hm_launch_part1(s, b, (uint32_t)((redo_cap + HM_T1 - 1) / HM_T1), V.out16, 1);
-                    HIPCHK(hipGetLastError());
-                }
-                /* the level's buckets from the filled regions, launched before
-                 * the one host sync of level 1 (its results are used only if
-                 * the level turns out clean: no error, no redo or region
-                 * overflow) */
-                auto buckets1 = [&]() -> int {
-                    hm_launch_level1_buckets(s, ba);
-                    HIPCHK(hipGetLastError());
-                    if (L > 1) HIPCHK(hipMemcpyAsync(ctx->host_aux, hist, F * 4, hipMemcpyDeviceToHost, s));
-                    return read_state(ctx);
-                };
-                if ((st = buckets1())) return st;
-                if ((st = take_error(ctx))) return st;
-                const uint64_t nredo = ctx->host_state[ST_REDO];
-                ctx->last_slow = (int64_t)nredo;
-                if (!from_tiles && nredo > redo_cap) {
-                    /* adversarial input (mostly polar / guard band): redo the
-                     * level with the exact chain fused into the kernel */
-                    HIPCHK(hipMemsetAsync(fill, 0, FS * 4, s));
-                    HIPCHK(hipMemsetAsync(ctx->state + ST_OVERFLOW, 0, 8, s));
-                    HIPCHK(hipMemsetAsync(xl.count, 0, 8, s));
-                    HIPCHK(hipMemsetAsync(ctx->state + ST_NSLOTS, 0, 8, s));   /* buckets1 again */
-                    /* hm_last_stats: the points this run resolves, not those
-                     * plus the first run's deferred ones (every point twice) */
-                    HIPCHK(hipMemsetAsync(ctx->state + ST_SLOW, 0, 8, s));
-                    hm_launch_part1(s, a, tiles_in, V.out16, 2);
-                    HIPCHK(hipGetLastError());
-                    if ((st = buckets1())) return st;
-                    if ((st = take_error(ctx))) return st;
-                }
-                if (!ctx->host_state[ST_OVERFLOW]) break;
-                /* a region overflowed: fill[] now holds the exact sizes (the
-                 * shard of every tile is fixed by its block id) */
-                if (attempt > 0) return HM_E_HIP;   /* cannot happen: the same points */
-                l1_reruns++;
-                HIPCHK(hipMemcpyAsync(hc, fill, FS * 4, hipMemcpyDeviceToHost, s));
-                if (ctx->debug_l1) HIPCHK(hipMemcpyAsync(hb, rcap, FS * 4, hipMemcpyDeviceToHost, s));
-                HIPCHK(hm_sync(s));
-                if (ctx->debug_l1) {
-                    /* HM_DEBUG_L1=1: the overflowing regions, and the sample behind them */
-                    for (int i = 0; i < FS; i++)
-                        if (hc[i] > hb[i])
-                            fprintf(stderr, "hm l1 overflow: digit %d shard %d fill %u cap %u hist %u stride %llu\n",
-                                    i % HM_D1, i / HM_D1, hc[i], hb[i], ctx->host_aux[i % HM_D1],
-                                    (unsigned long long)stride);
-                }
-                for (int i = 0; i < FS; i++) hc[i] += 64;
-            }
-            nx = ctx->host_state[ST_XCOUNT];
-            if (nx > xl.cap) {
-                /* more kept out-of-square points than the list held: rebuild it */
-                xl.cap = nx;
-                ENSURE(B_X_ROW, xl.cap * 8, xl.row);
-                ENSURE(B_X_COL, xl.cap * 8, xl.col);
-                ENSURE(B_X_IDX, xl.cap * 8, xl.idx);
-                HIPCHK(hipMemsetAsync(xl.count, 0, sizeof(unsigned long long), s));
-                hm_launch_collect_exotic(s, lat, lon, rows, cols, keep, n, Z, xl);
-                HIPCHK(hipGetLastError());
-                if ((st = read_state(ctx))) return st;
-                nx = ctx->host_state[ST_XCOUNT];
-                if (nx > xl.cap) return HM_E_HIP;   /* cannot happen: the same points */
-            }
-            nhot = hot_on ? (uint32_t)(ctx->host_state[ST_NHOT] & 0xFFFFFFFFull) : 0u;
-            if (!nhot) hot_mid = false;
-            /* levels 2.. may take the spread plan (the level-1 pass is the
-             * same under both: its output is u32 keys whenever L > 1) */
-            if (hot_mid) {
-                /* the plan stays z5 -> z11 -> zb: the hot tiles are zoom-11 buckets */
-            } else if (L > 1 && !nhot) {
-                spread_replan(ctx->host_aux, F, (double)n, zb, zs, &L, ctx->spread_min_keys, true);
-            } else if (L > 1) {
-                /* with hot tiles the rest is the cloud's sparse background: 3
-                 * zooms per level unless it is tiny (a 6-zoom level scatters
-                 * each 8192-key item over 4096 children, runs of ~1 key); the
-                 * hot tiles then join at the last level.  (host_aux holds the
-                 * cold digits' sampled counts: the hot samples were taken off) */
-                double cold = 0;
-                for (int i = 0; i < F; i++) cold += ctx->host_aux[i];
-                spread_replan(ctx->host_aux, F, cold * (double)stride, zb, zs, &L, ctx->spread_min_cold, false);
-            }
-            spread = L > 2 && zs[1] - zs[0] < HM_LEVEL_ZOOMS;
-            ctx->last_levels = L;
-            V.count = (uint32_t)(ctx->host_state[ST_LTOT] >> 32);
-            V.items = (uint32_t)(ctx->host_state[ST_LTOT] & 0xFFFFFFFFull);
-            if (L == 1) nslots = (uint32_t)(ctx->host_state[ST_NSLOTS] & 0xFFFFFFFFull);
-            level_keys = total_cap;
-            HmBuckets& b = B[0];
-            b.count = V.count;
-            b.nkeys = ba.out.nkeys;
-            b.nruns = ba.out.nruns;
-            b.rbase = ba.out.rbase;
-            b.keybase = ba.out.keybase;
-            b.item_begin = ba.out.item_begin;
-            b.digit = ba.out.digit;
-            b.coord = ba.out.coord;
-            b.slots = (L == 1) ? slots : nullptr;
-            runs_cur.run = ba.runs;
-            runs_cur.excl = ba.excl;
-            {
-                uint4* desc;
-                ENSURE(B_DESC0 + 0, ((uint64_t)V.items + 1) * 2 * sizeof(uint4), desc);
-                b.desc = desc;
-                if (L > 1) ENSURE(B_SEG, ((uint64_t)V.items + 1) * 16 * sizeof(uint32_t), seg1);
-                hm_launch_items(s, b, runs_cur, V.items, (L == 1) ? ta : HM_TN, desc, L > 1 ? seg1 : nullptr);
-                HIPCHK(hipGetLastError());
-            }
-            keys_cur = kout;
-            parent_item_begin = ba.out.item_begin;
-            parent_coord = ba.out.coord;
-            nparents = V.count;
-            slot_k ^= 1;
-            continue;
-        }
-        /* ---- levels >= 2 ---- */
-        const uint64_t ntiles = lv[l - 1].items;
-        /* run-counter shards: up to 32 (a hot child takes one returning atomic
-         * per parent work item; one counter per child made k_partition 16%
-         * slower), fewer when the dense child space is large; <= 2^25 */
-        /* with hot tiles (their children skip this level) or the spread plan,
-         * no child is hot: one counter per child, and the partition kernels'
-         * run-slot atomics coalesce (lanes own consecutive digits) */
-        /* a child-contiguous level (HM_PN_CONTIG): the middle level of a
-         * 3-level plan without hot tiles (Z >= 19) writes each child's keys
-         * as ONE run, so the last level reads every item from <= 8 runs
-         * (k_partition_fr) instead of streaming runs of a few keys each */
-        /* (with mid-level hot tiles the cold keys go above every level-1
-         * position, where the hot tiles' keys are: cbase_off) */
-        /* level 1's positions end at its regions' total capacity (k_l1_sizes),
-         * or, after an overflow re-run, at the exact sizes' total (level_keys) */
-        const uint64_t l1_total = l1_reruns ? level_keys : ctx->host_state[ST_L1TOTAL];
-        const bool contig = ctx->contig && l == 1 && L == 3 && (!nhot || hot_mid) && !V.out16 && seg1 != nullptr &&
-                            (!hot_mid || l1_total + (uint64_t)n < 0xFFF00000ull);
-        int sb = ctx->run_shard_bits >= 0 ? ctx->run_shard_bits : ((nhot || spread) ? 0 : HM_RUN_SHARD_BITS);
-        if (contig) sb = 0;
-        while (sb > 0 && (V.nchildren << sb) > (1ull << 25)) sb--;
-        const uint64_t run_cap = (ntiles + ((uint64_t)nparents << sb)) << V.dbits;
-        if (run_cap >= (1ull << 32)) return HM_E_NOMEM;
+/* level l's seven bucket arrays (B_l), cap entries each */
+int CountCall::bucket_arrays(int l, uint64_t cap, HmCompactOut& out)
+{
+    ENSURE(B_BK0 + l * 8 + 0, cap * 4, out.nkeys);
+    ENSURE(B_BK0 + l * 8 + 1, cap * 4, out.nruns);
+    ENSURE(B_BK0 + l * 8 + 2, cap * 4, out.rbase);
+    ENSURE(B_BK0 + l * 8 + 3, cap * 4, out.item_begin);
+    ENSURE(B_BK0 + l * 8 + 4, cap * 4, out.digit);
+    ENSURE(B_BK0 + l * 8 + 5, cap * 8, out.coord);
+    ENSURE(B_BK0 + l * 8 + 6, cap * 4, out.keybase);
+    return HM_OK;
+}
 
-        /* outputs of the level's partition kernel: keys at the item's global
-         * positions, and sharded runs */
-        void* kout;
-        uint2* runs_sh;
-        uint32_t* nruns;
-        const uint64_t nkeys_out = level_keys;
-        /* with hot tiles the last level's keys go where level 1 put the hot
-         * tiles' (B); a 3-level plan's middle level then takes a third array */
-        const bool hot3 = nhot && L == 3 && !hot_mid;
-        const int kslot = hot3 ? (l == 1 ? B_KEYS_C : B_KEYS_B) : (slot_k ? B_KEYS_B : B_KEYS_A);
-        ENSURE(kslot, std::max<uint64_t>(nkeys_out + 8, (hot_mid && l == 1) ? l2_elems : 0) * (V.out16 ? 2 : 4), kout);
-        ENSURE(B_RUNS_SH, run_cap * sizeof(uint2), runs_sh);
-        ENSURE(B_NRUNS, (V.nchildren << sb) * sizeof(uint32_t), nruns);
-        uint32_t* rs_big;
-        ENSURE(B_RS_BIG, (HM_RS_BIG_MAX + 1) * sizeof(uint32_t), rs_big);
-        {
-            /* the level's zeroed counters in one launch */
-            HmFill zf;
-            zf.k = 0;
-            hm_fill_add(zf, nruns, 0, (V.nchildren << sb) * sizeof(uint32_t));
-            hm_fill_add(zf, rs_big + HM_RS_BIG_MAX, 0, sizeof(uint32_t));   /* the run scan's big-child count */
-            hm_launch_fill(s, zf);
-        }
+/* B_l from the level's bucket arrays and its read-back count, the work items
+ * of the next stage (k_items), and the hand-off to it.  seg_slot: the arena
+ * slot of the items' run tables (B_SEG, B_SEG2), or -1 for none */
+int CountCall::publish(int l, const HmCompactOut& out, HmRuns runs, void* keys, uint64_t level_keys, int seg_slot)
+{
+    const Level& V = lv[l];
+    const bool last = l == L - 1;
+    HmBuckets& b = B[l];
+    b.count = V.count;
+    b.nkeys = out.nkeys;
+    b.nruns = out.nruns;
+    b.rbase = out.rbase;
+    b.keybase = out.keybase;
+    b.item_begin = out.item_begin;
+    b.digit = out.digit;
+    b.coord = out.coord;
+    b.slots = last ? slots : nullptr;
+    uint4* desc;
+    ENSURE(B_DESC0 + l, ((uint64_t)V.items + 1) * 2 * sizeof(uint4), desc);
+    b.desc = desc;
+    hand.seg = nullptr;
+    if (seg_slot >= 0) ENSURE(seg_slot, ((uint64_t)V.items + 1) * 16 * sizeof(uint32_t), hand.seg);
+    hm_launch_items(s, b, runs, V.items, last ? ta : HM_TN, desc, hand.seg);
+    HIPCHK(hipGetLastError());
+    hand.keys = keys;
+    hand.runs = runs;
+    hand.parent_item_begin = out.item_begin;
+    hand.parent_coord = out.coord;
+    hand.nparents = V.count;
+    hand.level_keys = level_keys;
+    hand.slot_k ^= 1;
+    return HM_OK;
+}
 
-        {
-            HmPartNArgs a;
-            memset(&a, 0, sizeof(a));
-            a.parent = B[l - 1];
-            a.keys_in = (const uint32_t*)keys_cur;
-            a.in = runs_cur;
-            a.dbits = V.dbits;
-            a.restbits = restbits;
-            a.shard_bits = sb;
-            a.keys_out = kout;
-            a.nruns_out = nruns;
-            a.runs_out = runs_sh;
-            a.items = lv[l - 1].items;
-            a.seg = l == 1 ? seg1 : seg2;
-            if (timing) HIPCHK(hipEventRecord(ev[5 + 2 * (l - 1)], s));
-            if (contig) {
-                /* child totals, their scan, then the partition proper */
-                uint64_t *ptl, *ttl;
-                ENSURE(B_PARTIAL, 4096 * sizeof(uint64_t), ptl);
-                ENSURE(B_TOTAL, 4 * sizeof(uint64_t), ttl);
-                ENSURE(B_CTOT, V.nchildren * 8, a.ctot);
-                ENSURE(B_CBASE, V.nchildren * 8, a.cbase);
-                ENSURE(B_CCUR, V.nchildren * 4, a.ccur);
-                HIPCHK(hipMemsetAsync(a.ctot, 0, V.nchildren * 8, s));
-                HIPCHK(hipMemsetAsync(a.ccur, 0, V.nchildren * 4, s));
-                a.mode = HM_PN_HIST;
-                a.cbase_off = hot_mid ? (uint32_t)l1_total : 0u;
-                hm_launch_partition_hist(s, a);
-                hm_launch_scan(s, (const uint64_t*)a.ctot, V.nchildren, ptl, (uint64_t*)a.cbase, ttl + 3);
-                a.mode = HM_PN_CONTIG;
-            }
-            hm_launch_partN(s, a, lv[l - 1].items, V.out16, (l == 1 && seg1 != nullptr) || (l == 2 && seg2 != nullptr));
-            HIPCHK(hipGetLastError());
-            if (timing) HIPCHK(hipEventRecord(ev[6 + 2 * (l - 1)], s));
-            npart = l;
-        }
+/* ---- level 1: projection + partition into per-digit regions ---- */
+int CountCall::level1()
+{
+    int st;
+    if ((st = begin_level(0))) return st;
+    Level1Work w;
+    if ((st = level1_setup(w))) return st;
+    if ((st = level1_size(w))) return st;
+    if ((st = level1_bucket_args(w))) return st;
+    if ((st = level1_run(w))) return st;
+    return level1_finish(w);
+}
 
-        /* run scan: sharded counters -> flat child-ordered runs + key prefix */
-        HmRsArgs ra;
-        memset(&ra, 0, sizeof(ra));
-        ra.nchildren = V.nchildren;
-        ra.dbits = V.dbits;
-        ra.shard_bits = sb;
-        ra.nruns = nruns;
-        ra.runs = runs_sh;
-        ra.parent_item_begin = parent_item_begin;
-        ra.item_keys = (l == L - 1) ? ta : HM_TN;
-        ra.sparse_max = (l == L - 1) ? HM_SP_MAX : 0u;
-        uint64_t *partial, *tot;
-        ENSURE(B_SHOFF, (V.nchildren << sb) * sizeof(uint32_t), ra.shoff);
-        ENSURE(B_NR, V.nchildren * sizeof(uint64_t), ra.nr);
-        uint64_t* runbase;
-        ENSURE(B_RUNBASE0 + l, V.nchildren * sizeof(uint64_t), runbase);
-        ra.runbase = runbase;
-        ENSURE(B_PARTIAL, 4096 * sizeof(uint64_t), partial);
-        tot = (uint64_t*)(ctx->state + ST_LTOT);
-        hm_launch_rs_count(s, ra);
-        /* hot tiles are children of the last level: of their z5 bucket at
-         * level 2, of their zs[1] ancestor (kept as a bucket, below) at level 3 */
-        const bool hot_level = nhot && l == (hot_mid ? 1 : L - 1);
-        if (hot_level) {
-            hr.dbits = V.dbits;
-            hr.nr = ra.nr;
-            hr.zp = zs[l - 1];
-            hr.c2b = (l == 2 && hot3) ? (const uint32_t*)ctx->bufs[B_C2B].p : nullptr;
-            hm_launch_hot_nr(s, hr);
-        }
-        /* a 3-level plan with hot tiles: each hot tile's zs[1] ancestor must be
-         * a level-2 bucket (its parent at level 3) even without cold keys */
-        uint8_t* force = nullptr;
-        if (hot3 && l == 1) {
-            ENSURE(B_HOT_FORCE, V.nchildren, force);
-            HIPCHK(hipMemsetAsync(force, 0, V.nchildren, s));
-            hr.dbits = V.dbits;
-            hr.zp = zs[1];
-            hm_launch_hot_force(s, hr, force);
-        }
-        ra.force = force;
-        hm_launch_scan(s, ra.nr, V.nchildren, partial, runbase, tot + 0);
-        HIPCHK(hipGetLastError());
-        unsigned long long* down = ctx->host_state + 2 * ST_COUNT;
-        /* the flat run list is sized by a bound, its length stays on the
-         * device (tot[0]): at most one run per (parent item, child) and per
-         * key, plus the hot tiles' region shards */
-        uint64_t nflat = std::min<uint64_t>(level_keys, (uint64_t)lv[l - 1].items << V.dbits) +
-                         (uint64_t)HM_MAX_HOT * HM_L1_SHARDS + 1;
-        ra.nflat_dev = tot + 0;
-        if (nflat * 24 > (8ull << 30)) {
-            /* a bound of more than 8 GiB of run buffers: read the count back */
-            HIPCHK(hipMemcpyAsync(down, tot, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-            HIPCHK(hm_sync(s));
-            nflat = down[0];
-            ra.nflat_dev = nullptr;
-        }
-        ra.nflat = nflat;
-        uint2* flat;
-        uint64_t* excl;
-        ENSURE(slot_k ? B_FLAT_B : B_FLAT_A, (nflat + 1) * sizeof(uint2), flat);
-        ENSURE(slot_k ? B_EXCL_B : B_EXCL_A, (nflat + 1) * sizeof(uint64_t), excl);
-        ENSURE(B_CNT, (nflat + 1) * sizeof(uint64_t), ra.cnt);
-        ra.flat = flat;
-        ra.excl = excl;
-        ra.big = rs_big;
-        ra.nbig = ra.big + HM_RS_BIG_MAX;   /* zeroed with nruns */
-        ra.big_min = ctx->rs_big_min;
-        hm_launch_rs_copy(s, ra);
-        if (hot_level) {
-            hr.runbase = runbase;
-            hr.flat = flat;
-            hr.cnt = ra.cnt;
-            hm_launch_hot_runs(s, hr);
-        }
-        hm_launch_scan(s, ra.cnt, nflat, partial, excl, tot + 1, ra.nflat_dev);
-        ra.total_keys = tot + 1;
-        uint32_t* cnkeys;
-        uint32_t* ckeybase;
-        uint64_t *vals, *prefix;
-        ENSURE(B_NKEYS, V.nchildren * sizeof(uint32_t), cnkeys);
-        ENSURE(B_KEYBASE, V.nchildren * sizeof(uint32_t), ckeybase);
-        ENSURE(B_VALS, V.nchildren * sizeof(uint64_t), vals);
-        ENSURE(B_PREFIX, V.nchildren * sizeof(uint64_t), prefix);
-        ra.nkeys = cnkeys;
-        ra.keybase = ckeybase;
-        ra.vals = vals;
-        hm_launch_rs_keys(s, ra);
-        hm_launch_scan(s, vals, V.nchildren, partial, prefix, tot + 2);
-        HIPCHK(hipGetLastError());
-
-        /* B_l arrays: sized by nchildren (upper bound of |B_l|) */
-        const uint64_t cap = V.nchildren + 1;
-        HmCompactArgs ca;
-        memset(&ca, 0, sizeof(ca));
-        ENSURE(B_BK0 + l * 8 + 0, cap * 4, ca.out.nkeys);
-        ENSURE(B_BK0 + l * 8 + 1, cap * 4, ca.out.nruns);
-        ENSURE(B_BK0 + l * 8 + 2, cap * 4, ca.out.rbase);
-        ENSURE(B_BK0 + l * 8 + 3, cap * 4, ca.out.item_begin);
-        ENSURE(B_BK0 + l * 8 + 4, cap * 4, ca.out.digit);
-        ENSURE(B_BK0 + l * 8 + 5, cap * 8, ca.out.coord);
-        ENSURE(B_BK0 + l * 8 + 6, cap * 4, ca.out.keybase);
-        uint32_t* child_begin;
-        ENSURE(B_CHILD0 + l, ((uint64_t)nparents + 1) * 4, child_begin);
-        ca.nchildren = V.nchildren;
-        ca.nparents = nparents;
-        ca.dbits = V.dbits;
-        ca.vals = vals;
-        ca.prefix = prefix;
-        ca.total = tot + 2;
-        ca.nkeys = cnkeys;
-        ca.nr = ra.nr;
-        ca.runbase = runbase;
-        ca.keybase = ckeybase;
-        ca.parent_coord = parent_coord;
-        ca.child_begin = child_begin;
-        if (hot3 && l == 1) ENSURE(B_C2B, V.nchildren * 4, ca.c2b);   /* child -> bucket, for level 3 */
-        if (l == L - 1) {
-            ENSURE(B_SLOTS, cap * 4, slots);
-            ENSURE(B_SLOTBKT, cap * 4, slot_bucket);
-            ca.slots = slots;
-            ca.nslots = ctx->state + ST_NSLOTS;
-            ca.slot_bucket = slot_bucket;
-        }
-        hm_launch_compact(s, ca);
-        HIPCHK(hipGetLastError());
-        if ((st = read_state(ctx))) return st;   /* the level's totals come with it (ST_LTOT) */
-        level_keys = ctx->host_state[ST_LTOT + 1];
-        const uint64_t tot_h = ctx->host_state[ST_LTOT + 2];
-        V.count = (uint32_t)(tot_h >> 32);
-        V.items = (uint32_t)(tot_h & 0xFFFFFFFFull);
-        if (l == L - 1) nslots = (uint32_t)(ctx->host_state[ST_NSLOTS] & 0xFFFFFFFFull);
-
-        HmBuckets& b = B[l];
-        b.count = V.count;
-        b.nkeys = ca.out.nkeys;
-        b.nruns = ca.out.nruns;
-        b.rbase = ca.out.rbase;
-        b.keybase = ca.out.keybase;
-        b.item_begin = ca.out.item_begin;
-        b.digit = ca.out.digit;
-        b.coord = ca.out.coord;
-        b.slots = (l == L - 1) ? slots : nullptr;
-        runs_cur.run = flat;
-        runs_cur.excl = excl;
-        {
-            uint4* desc;
-            ENSURE(B_DESC0 + l, ((uint64_t)V.items + 1) * 2 * sizeof(uint4), desc);
-            b.desc = desc;
-            /* after a child-contiguous level every item of the next spans one run */
-            seg2 = nullptr;
-            if (contig) ENSURE(B_SEG2, ((uint64_t)V.items + 1) * 16 * sizeof(uint32_t), seg2);
-            hm_launch_items(s, b, runs_cur, V.items, (l == L - 1) ? ta : HM_TN, desc, seg2);
-            HIPCHK(hipGetLastError());
-        }
-
-        keys_cur = kout;
-        parent_item_begin = ca.out.item_begin;
-        parent_coord = ca.out.coord;
-        nparents = V.count;
-        slot_k ^= 1;
+/* level 1's buffers, the call's one fill dispatch, the sample pass and the
+ * hot-tile selection */
+int CountCall::level1_setup(Level1Work& w)
+{
+    const Level& V = lv[0];
+    /* the call's state words and level 1's zeroed buffers: one fill dispatch,
+     * launched before level 1's sampling */
+    HmFill f1;
+    memset(&f1, 0, sizeof(f1));
+    hm_fill_add(f1, ctx->state + 1, 0, (ST_COUNT - 1) * sizeof(unsigned long long));
+    hm_fill_add(f1, ctx->state + ST_ERR, 0xFF, sizeof(unsigned long long));
+    static_assert(ST_ERR == 0, "error word first");
+    w.F = 1 << V.dbits;
+    uint32_t* fill;
+    ENSURE(B_L1_FILL, FS * 4, fill);
+    ENSURE(B_L1_RBASE, FS * 4, w.rbase);
+    ENSURE(B_L1_RCAP, FS * 4, w.rcap);
+    ENSURE(B_L1_HIST, HM_D1 * 4, w.hist);
+    ENSURE(B_L1_SMASK, HM_D1, w.smask);
+    uint32_t* const hist = w.hist;
+    uint4* l1slot = nullptr;   /* k_l1_fast's slot table (lat/lon input) */
+    if (!from_tiles) ENSURE(B_L1_SLOT, (size_t)FS * sizeof(uint4), l1slot);
+    /* hot tiles are level-2 buckets: zoom zs[1], a dense sample
+     * histogram of <= 4^11 tiles.  In the two-level plan (level 1 at
+     * z1, the last at zb) they skip every partition after level 1; in
+     * a three-level plan (zmax 19-21: z5 -> z11 -> zb) they skip level 2
+     * and join level 3 with the level-2 buckets (HM_HOT_MID) */
+    hot_mid = ctx->hot && ctx->hot_mid && L == 3 && zs[1] <= 11 && zs[0] == HM_Z1 && n > 0 && V.dbits == 2 * HM_Z1;
+    hot_on = hot_mid || (ctx->hot && L == 2 && zb <= 11 && zs[0] == HM_Z1 && n > 0 && V.dbits == 2 * HM_Z1);
+    hz = hot_mid ? zs[1] : zb;
+    uint32_t* redo_idx = nullptr;
+    w.redo_rows = w.redo_cols = nullptr;
+    if (!from_tiles) {
+        ENSURE(B_REDO_IDX, redo_cap * sizeof(uint32_t), redo_idx);
+        ENSURE(B_REDO_ROWS, redo_cap * sizeof(int64_t), w.redo_rows);
+        ENSURE(B_REDO_COLS, redo_cap * sizeof(int64_t), w.redo_cols);
     }
-    if (timing) HIPCHK(hipEventRecord(ev[nev], s));
-    nev++;
+    HmPart1Args& a = w.a;
+    memset(&a, 0, sizeof(a));
+    a.lat = lat;
+    a.lon = lon;
+    a.rows_in = rows;
+    a.cols_in = cols;
+    a.keep = keep;
+    a.n = n;
+    a.Z = Z;
+    a.dbits = V.dbits;
+    a.restbits = 2 * (Z - zs[0]);
+    a.fill = fill;
+    a.rbase = w.rbase;
+    a.rcap = w.rcap;
+    a.smask = w.smask;
+    a.l1slot = l1slot;
+    a.overflow = ctx->state + ST_OVERFLOW;
+    a.err_word = ctx->state + ST_ERR;
+    a.x = xl;
+    a.slow_count = ctx->state + ST_SLOW;
+    a.redo_idx = redo_idx;
+    a.redo_count = ctx->state + ST_REDO;
+    a.redo_cap = redo_cap;
+    /* region sizes: a sampled digit histogram with a generous margin */
+    /* ~256K samples (1M samples above 2^28 points took 90 us per 1e9-point
+     * count; the regions' 8-sigma margins scale with sqrt(stride)) */
+    /* (2^16 samples below 2^24 points, where the sample pass's ~30 us
+     * is a batch's cost; the regions' slack scales with the stride) */
+    const int slog = n < (1ll << 24) ? std::min(ctx->sample_log2, 16) : ctx->sample_log2;
+    const uint64_t stride = w.stride = std::max<uint64_t>(1, (uint64_t)n >> slog);
+    hm_fill_add(f1, hist, 0, HM_D1 * 4);
+    hm_fill_add(f1, fill, 0, FS * 4);
+    uint32_t* hot_counts = nullptr;
+    uint32_t* hot_tiles = nullptr;
+    uint32_t* hot_hash = nullptr;
+    uint8_t* hot_parent = nullptr;
+    uint32_t* hot_n = (uint32_t*)(ctx->state + ST_NHOT);
+    if (hot_on) {
+        ENSURE(B_HOT_COUNTS, (4ull << (2 * hz)), hot_counts);
+        ENSURE(B_HOT, (HM_MAX_HOT + HM_HOT_SLOTS + 2 * HM_HOT_CAND + 1) * 4, hot_tiles);
+        ENSURE(B_HOT_PARENT, HM_MAX_F1, hot_parent);
+        hot_hash = hot_tiles + HM_MAX_HOT;
+        hm_fill_add(f1, hot_counts, 0, 4ull << (2 * hz));
+        hm_fill_add(f1, hot_hash + HM_HOT_SLOTS + 2 * HM_HOT_CAND, 0, 4);   /* candidates */
+        hm_fill_add(f1, hot_parent, 0, HM_MAX_F1);
+        a.hot_z = hz;
+        a.hot_bytes = hot_mid ? 4 : 2;
+        a.hot_hash = hot_hash;
+        a.hot_n = hot_n;
+    } else {
+        a.hot_z = -1;
+    }
+    hm_launch_fill(s, f1);
+    if (n > 0) hm_launch_sample_digits(s, a, stride, hist, hot_counts);
+    HIPCHK(hipGetLastError());
+    if (hot_on) {
+        hr.tiles = hot_tiles;
+        hr.n = hot_n;
+        hr.zb = hz;
+        hr.z1 = zs[0];
+        hr.fill = fill;
+        hr.rbase = w.rbase;
+        HmHotArgs ha;
+        ha.counts = hot_counts;
+        ha.zb = hz;
+        ha.z1 = zs[0];
+        const uint64_t m = ((uint64_t)n + stride - 1) / stride;
+        ha.thresh = (uint32_t)std::max<double>(
+            {1.0, ceil((double)m / ctx->hot_inv_share), ceil(ctx->hot_min_keys / (double)stride)});
+        ha.tiles = hot_tiles;
+        ha.hist = hist;
+        ha.hotparent = hot_parent;
+        ha.n = hot_n;
+        ha.hash = hot_hash;
+        ha.cand = hot_hash + HM_HOT_SLOTS;
+        hm_launch_hot_select(s, ha);
+        HIPCHK(hipGetLastError());
+    }
+    return HM_OK;
+}
 
-    /* final aggregation over B_L */
-    HmOut o;
+/* the regions' sizes (on the device) and the host's bound of their total,
+ * which sizes the key buffer: w.total_cap */
+int CountCall::level1_size(Level1Work& w)
+{
+    const HmPart1Args& a = w.a;
+    const int F = w.F;
+    const uint64_t stride = w.stride;
+    int st;
+    /* the region sizes are computed on the device (k_l1_sizes); the key
+     * buffer takes the host's bound of their total: est sums to at
+     * most nn (a hot tile's samples leave its cold digit), at most M
+     * (digit, shard) entries are non-empty, and sum sqrt(e stride) <=
+     * sqrt(M nn stride) (Cauchy-Schwarz) */
+    const double nn = (double)n + (double)(F + (hot_on ? HM_MAX_HOT : 0)) * (double)stride;
+    const double M = F + std::min((double)F, nn / ((double)HM_L1_SHARD_TILES * HM_T1)) * (HM_L1_SHARDS - 1) +
+                     (hot_on ? (double)HM_MAX_HOT * HM_L1_SHARDS : 0.0);
+    double bound = nn * 17.0 / 16.0 + 8.0 * sqrt(M * nn * (double)stride) + M * 2.0 * HM_T1 +
+                   (double)(F + (hot_on ? HM_MAX_HOT : 0)) * HM_L1_ZERO_SAMPLES * (double)stride + 1024.0;
+    hm_launch_l1_sizes(s, w.hist, F, hot_on ? (uint32_t*)(ctx->state + ST_NHOT) : nullptr, stride, w.rcap, w.rbase,
+                       w.smask, ctx->state + ST_L1TOTAL);
+    if (a.l1slot) hm_launch_l1_slots(s, a);
+    HIPCHK(hipGetLastError());
+    if (bound >= (double)0xFFF00000ull) {
+        /* the bound passes the u32 key positions (n above ~1.5e9):
+         * read the exact total of the sized regions instead */
+        if ((st = read_state(ctx))) return st;
+        bound = (double)ctx->host_state[ST_L1TOTAL] + 1024.0;
+        if (bound >= (double)0xFFF00000ull) return HM_FALLBACK;   /* key positions are u32 */
+    }
+    w.total_cap = (uint64_t)bound;
+    return HM_OK;
+}
+
+/* the non-empty digits are the level's buckets, one run each */
+int CountCall::level1_bucket_args(Level1Work& w)
+{
+    const Level& V = lv[0];
+    HmL1Args& ba = w.ba;
+    int st;
+    memset(&ba, 0, sizeof(ba));
+    const uint64_t cap = (uint64_t)w.F + 1;
+    if ((st = bucket_arrays(0, cap, ba.out))) return st;
+    ENSURE(B_FLAT_A, (uint64_t)FS * sizeof(uint2) + 8, ba.runs);
+    ENSURE(B_EXCL_A, (uint64_t)FS * sizeof(uint64_t) + 8, ba.excl);
+    ENSURE(B_CHILD0, 2 * 4, ba.child_begin);
+    ba.F = w.F;
+    ba.dbits = V.dbits;
+    ba.fill = w.a.fill;
+    ba.rbase = w.rbase;
+    ba.smask = w.smask;
+    ba.item_keys = (L == 1) ? ta : HM_TN;
+    ba.sparse_max = (L == 1) ? HM_SP_MAX : 0u;
+    ba.total = ltot();
+    if (hot_on) {   /* hot parents all zero when no tile turned out hot */
+        uint32_t* d2b;
+        ENSURE(B_D2B, HM_MAX_F1 * 4, d2b);
+        ba.hotparent = hr.tiles ? (const uint8_t*)ctx->bufs[B_HOT_PARENT].p : nullptr;
+        ba.d2b = d2b;
+        hr.d2b = d2b;
+    }
+    if (L == 1) {
+        ENSURE(B_SLOTS, cap * 4, slots);
+        ENSURE(B_SLOTBKT, cap * 4, slot_bucket);
+        ba.slots = slots;
+        ba.nslots = ctx->state + ST_NSLOTS;
+        ba.slot_bucket = slot_bucket;
+    }
+    return HM_OK;
+}
+
+/* a region overflowed: fill[] now holds the exact sizes (the shard of every
+ * tile is fixed by its block id); read them back (one host wait) and lay the
+ * regions out again */
+int CountCall::level1_resize(Level1Work& w)
+{
+    const HmPart1Args& a = w.a;
+    /* pinned host scratch: caps [FS] | bases [FS] */
+    uint32_t* hc = ctx->host_aux + HM_D1;
+    uint32_t* hb = hc + HM_D1 * HM_L1_SHARDS;
+    l1_reruns++;
+    HIPCHK(hipMemcpyAsync(hc, a.fill, FS * 4, hipMemcpyDeviceToHost, s));
+    if (ctx->debug_l1) HIPCHK(hipMemcpyAsync(hb, w.rcap, FS * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hm_sync(s));
+    if (ctx->debug_l1) {
+        /* HM_DEBUG_L1=1: the overflowing regions, and the sample behind them */
+        for (int i = 0; i < FS; i++)
+            if (hc[i] > hb[i])
+                fprintf(stderr, "hm l1 overflow: digit %d shard %d fill %u cap %u hist %u stride %llu\n", i % HM_D1,
+                        i / HM_D1, hc[i], hb[i], ctx->host_aux[i % HM_D1], (unsigned long long)w.stride);
+    }
+    for (int i = 0; i < FS; i++) hc[i] += 64;
+    /* a digit's shards stay consecutive: its keys' logical
+     * positions are one range (k_level1_buckets) */
+    w.total_cap = 0;
+    for (int d = 0; d < HM_D1; d++)
+        for (int sh = 0; sh < HM_L1_SHARDS; sh++) {
+            hb[hm_l1i(d, sh)] = (uint32_t)w.total_cap;
+            w.total_cap += hc[hm_l1i(d, sh)];
+        }
+    if (w.total_cap >= 0xFFF00000ull) return HM_FALLBACK;
+    HIPCHK(hipMemcpyAsync(w.rcap, hc, FS * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(w.rbase, hb, FS * 4, hipMemcpyHostToDevice, s));
+    if (a.l1slot) hm_launch_l1_slots(s, a);   /* the table holds the regions' bases and sizes */
+    return HM_OK;
+}
+
+/* lat/lon input: the points the fast path deferred, resolved exactly (k_redo)
+ * and partitioned as tile input */
+int CountCall::level1_redo(Level1Work& w)
+{
+    HmRedoArgs ra;
+    ra.lat = lat;
+    ra.lon = lon;
+    ra.keep = keep;
+    ra.Z = Z;
+    ra.redo_idx = w.a.redo_idx;
+    ra.redo_count = ctx->state + ST_REDO;
+    ra.rows_out = w.redo_rows;
+    ra.cols_out = w.redo_cols;
+    ra.out_count = ctx->state + ST_REDO_OUT;
+    ra.err_word = ctx->state + ST_ERR;
+    ra.x = xl;
+    ra.cap = redo_cap;
+    hm_launch_redo(s, ra, redo_cap);
+    HIPCHK(hipGetLastError());
+    /* the deferred points, resolved exactly, as tile input; the
+     * launch covers the list's capacity and reads its length
+     * on the device (no host round trip) */
+    HmPart1Args b = w.a;
+    b.lat = nullptr;
+    b.lon = nullptr;
+    b.rows_in = w.redo_rows;
+    b.cols_in = w.redo_cols;
+    b.keep = nullptr;
+    b.n = (int64_t)redo_cap;
+    b.n_dev = ctx->state + ST_REDO_OUT;
+    hm_launch_part1(s, b, (uint32_t)((redo_cap + HM_T1 - 1) / HM_T1), lv[0].out16, 1);
+    HIPCHK(hipGetLastError());
+    return HM_OK;
+}
+
+/* the level's buckets from the filled regions, launched before the one host
+ * sync of level 1 (its results are used only if the level turns out clean:
+ * no error, no redo or region overflow) */
+int CountCall::level1_buckets(Level1Work& w)
+{
+    hm_launch_level1_buckets(s, w.ba);
+    HIPCHK(hipGetLastError());
+    if (L > 1) HIPCHK(hipMemcpyAsync(ctx->host_aux, w.hist, w.F * 4, hipMemcpyDeviceToHost, s));
+    return read_state(ctx);
+}
+
+/* the attempts: the partition, its buckets and the level's one host sync;
+ * again with the exact chain fused in if the redo list overflowed, and once
+ * more from the top, with exact region sizes, if a region did */
+int CountCall::level1_run(Level1Work& w)
+{
+    const Level& V = lv[0];
+    HmPart1Args& a = w.a;
+    int st;
+    for (int attempt = 0;; attempt++) {
+        ENSURE(hand.slot_k ? B_KEYS_B : B_KEYS_A, (w.total_cap + 8) * (V.out16 ? 2 : 4), w.kout);
+        a.keys_out = w.kout;
+        if (hot_on) {
+            /* hot keys: straight into level 2's output key array (level 2
+             * writes the cold keys' positions of it): u16 when that is the
+             * last level's, u32 for mid-level hot tiles -- whose array
+             * also holds the child-contiguous cold keys above every
+             * level-1 position (l2_elems) */
+            void* kh = nullptr;
+            if (hot_mid) l2_elems = w.total_cap + (uint64_t)n + 16;
+            ENSURE(hand.slot_k ? B_KEYS_A : B_KEYS_B, hot_mid ? l2_elems * 4 : (w.total_cap + 8) * 2, kh);
+            a.keys_hot = kh;
+        }
+        if (attempt > 0) {
+            /* (the first attempt's are zero from the call's fill) */
+            HIPCHK(hipMemsetAsync(a.fill, 0, FS * 4, s));
+            /* ST_XCOUNT .. ST_OVERFLOW (XCOUNT, SLOW, REDO, REDO_OUT, OVERFLOW;
+             * CURSOR, NSLOTS, XCURSOR are still 0 here) in one memset */
+            static_assert(ST_XCOUNT == 1 && ST_OVERFLOW == 8 && ST_NHOT > ST_OVERFLOW, "level-1 words");
+            HIPCHK(hipMemsetAsync(ctx->state + ST_XCOUNT, 0, 8 * 8, s));
+        }
+        if (timing) HIPCHK(hipEventRecord(ctx->ev[0], s));
+        hm_launch_part1(s, a, tiles_in, V.out16, from_tiles ? 1 : 0);
+        HIPCHK(hipGetLastError());
+        if (timing) HIPCHK(hipEventRecord(ctx->ev[1], s));
+        nev = 2;
+        if (!from_tiles && (st = level1_redo(w))) return st;
+        if ((st = level1_buckets(w))) return st;
+        if ((st = take_error(ctx))) return st;
+        const uint64_t nredo = ctx->host_state[ST_REDO];
+        ctx->last_slow = (int64_t)nredo;
+        if (!from_tiles && nredo > redo_cap) {
+            /* adversarial input (mostly polar / guard band): redo the
+             * level with the exact chain fused into the kernel */
+            HIPCHK(hipMemsetAsync(a.fill, 0, FS * 4, s));
+            HIPCHK(hipMemsetAsync(ctx->state + ST_OVERFLOW, 0, 8, s));
+            HIPCHK(hipMemsetAsync(xl.count, 0, 8, s));
+            HIPCHK(hipMemsetAsync(ctx->state + ST_NSLOTS, 0, 8, s));   /* level1_buckets again */
+            /* hm_last_stats: the points this run resolves, not those
+             * plus the first run's deferred ones (every point twice) */
+            HIPCHK(hipMemsetAsync(ctx->state + ST_SLOW, 0, 8, s));
+            hm_launch_part1(s, a, tiles_in, V.out16, 2);
+            HIPCHK(hipGetLastError());
+            if ((st = level1_buckets(w))) return st;
+            if ((st = take_error(ctx))) return st;
+        }
+        if (!ctx->host_state[ST_OVERFLOW]) break;
+        if (attempt > 0) return HM_E_HIP;   /* cannot happen: the same points */
+        if ((st = level1_resize(w))) return st;
+    }
+    return HM_OK;
+}
+
+/* after the level's sync: the exotic list rebuilt if it overflowed, the hot
+ * tiles found, the plan of levels 2.. revised, B_1 and its items published */
+int CountCall::level1_finish(Level1Work& w)
+{
+    Level& V = lv[0];
+    const int F = w.F;
+    int st;
+    nx = ctx->host_state[ST_XCOUNT];
+    if (nx > xl.cap) {
+        /* more kept out-of-square points than the list held: rebuild it */
+        xl.cap = nx;
+        ENSURE(B_X_ROW, xl.cap * 8, xl.row);
+        ENSURE(B_X_COL, xl.cap * 8, xl.col);
+        ENSURE(B_X_IDX, xl.cap * 8, xl.idx);
+        HIPCHK(hipMemsetAsync(xl.count, 0, sizeof(unsigned long long), s));
+        hm_launch_collect_exotic(s, lat, lon, rows, cols, keep, n, Z, xl);
+        HIPCHK(hipGetLastError());
+        if ((st = read_state(ctx))) return st;
+        nx = ctx->host_state[ST_XCOUNT];
+        if (nx > xl.cap) return HM_E_HIP;   /* cannot happen: the same points */
+    }
+    nhot = hot_on ? (uint32_t)(ctx->host_state[ST_NHOT] & 0xFFFFFFFFull) : 0u;
+    if (!nhot) hot_mid = false;
+    /* levels 2.. may take the spread plan (the level-1 pass is the
+     * same under both: its output is u32 keys whenever L > 1) */
+    if (hot_mid) {
+        /* the plan stays z5 -> z11 -> zb: the hot tiles are zoom-11 buckets */
+    } else if (L > 1 && !nhot) {
+        spread_replan(ctx->host_aux, F, (double)n, zb, zs, &L, ctx->spread_min_keys, true);
+    } else if (L > 1) {
+        /* with hot tiles the rest is the cloud's sparse background: 3
+         * zooms per level unless it is tiny (a 6-zoom level scatters
+         * each 8192-key item over 4096 children, runs of ~1 key); the
+         * hot tiles then join at the last level.  (host_aux holds the
+         * cold digits' sampled counts: the hot samples were taken off) */
+        double cold = 0;
+        for (int i = 0; i < F; i++) cold += ctx->host_aux[i];
+        spread_replan(ctx->host_aux, F, cold * (double)w.stride, zb, zs, &L, ctx->spread_min_cold, false);
+    }
+    spread = L > 2 && zs[1] - zs[0] < HM_LEVEL_ZOOMS;
+    ctx->last_levels = L;
+    V.count = (uint32_t)(ctx->host_state[ST_LTOT] >> 32);
+    V.items = (uint32_t)(ctx->host_state[ST_LTOT] & 0xFFFFFFFFull);
+    if (L == 1) nslots = (uint32_t)(ctx->host_state[ST_NSLOTS] & 0xFFFFFFFFull);
+    return publish(0, w.ba.out, HmRuns{w.ba.runs, w.ba.excl}, w.kout, w.total_cap, L > 1 ? B_SEG : -1);
+}
+
+/* ---- levels >= 2 (l: the level's index, level 2 is l = 1) ---- */
+int CountCall::level(int l)
+{
+    int st;
+    if ((st = begin_level(l))) return st;
+    LevelWork w;
+    if ((st = level_begin(l, w))) return st;
+    if ((st = level_partition(l, w))) return st;
+    if ((st = level_runscan(l, w))) return st;
+    return level_compact(l, w);
+}
+
+/* the level's choices (shard bits, child-contiguous or not, key slot), the
+ * partition's output buffers and the level's zeroed counters */
+int CountCall::level_begin(int l, LevelWork& w)
+{
+    const Level& V = lv[l];
+    w.restbits = 2 * (Z - zs[l]);
+    const uint64_t ntiles = lv[l - 1].items;
+    /* run-counter shards: up to 32 (a hot child takes one returning atomic
+     * per parent work item; one counter per child made k_partition 16%
+     * slower), fewer when the dense child space is large; <= 2^25 */
+    /* with hot tiles (their children skip this level) or the spread plan,
+     * no child is hot: one counter per child, and the partition kernels'
+     * run-slot atomics coalesce (lanes own consecutive digits) */
+    /* a child-contiguous level (HM_PN_CONTIG): the middle level of a
+     * 3-level plan without hot tiles (Z >= 19) writes each child's keys
+     * as ONE run, so the last level reads every item from <= 8 runs
+     * (k_partition_fr) instead of streaming runs of a few keys each */
+    /* (with mid-level hot tiles the cold keys go above every level-1
+     * position, where the hot tiles' keys are: cbase_off) */
+    /* level 1's positions end at its regions' total capacity (k_l1_sizes),
+     * or, after an overflow re-run, at the exact sizes' total (level_keys) */
+    w.l1_total = l1_reruns ? hand.level_keys : ctx->host_state[ST_L1TOTAL];
+    w.contig = ctx->contig && l == 1 && L == 3 && (!nhot || hot_mid) && !V.out16 && hand.seg != nullptr &&
+               (!hot_mid || w.l1_total + (uint64_t)n < 0xFFF00000ull);
+    int sb = ctx->run_shard_bits >= 0 ? ctx->run_shard_bits : ((nhot || spread) ? 0 : HM_RUN_SHARD_BITS);
+    if (w.contig) sb = 0;
+    while (sb > 0 && (V.nchildren << sb) > (1ull << 25)) sb--;
+    w.sb = sb;
+    const uint64_t run_cap = (ntiles + ((uint64_t)hand.nparents << sb)) << V.dbits;
+    if (run_cap >= (1ull << 32)) return HM_E_NOMEM;
+
+    /* outputs of the level's partition kernel: keys at the item's global
+     * positions, and sharded runs */
+    const uint64_t nkeys_out = hand.level_keys;
+    /* with hot tiles the last level's keys go where level 1 put the hot
+     * tiles' (B); a 3-level plan's middle level then takes a third array */
+    w.hot3 = nhot && L == 3 && !hot_mid;
+    const int kslot = w.hot3 ? (l == 1 ? B_KEYS_C : B_KEYS_B) : (hand.slot_k ? B_KEYS_B : B_KEYS_A);
+    ENSURE(kslot, std::max<uint64_t>(nkeys_out + 8, (hot_mid && l == 1) ? l2_elems : 0) * (V.out16 ? 2 : 4), w.kout);
+    ENSURE(B_RUNS_SH, run_cap * sizeof(uint2), w.runs_sh);
+    ENSURE(B_NRUNS, (V.nchildren << sb) * sizeof(uint32_t), w.nruns);
+    ENSURE(B_RS_BIG, (HM_RS_BIG_MAX + 1) * sizeof(uint32_t), w.rs_big);
+    /* the level's zeroed counters in one launch */
+    HmFill zf;
+    zf.k = 0;
+    hm_fill_add(zf, w.nruns, 0, (V.nchildren << sb) * sizeof(uint32_t));
+    hm_fill_add(zf, w.rs_big + HM_RS_BIG_MAX, 0, sizeof(uint32_t));   /* the run scan's big-child count */
+    hm_launch_fill(s, zf);
+    return HM_OK;
+}
+
+/* the partition of B_{l-1}'s keys by the level's digit; a child-contiguous
+ * level first takes the child totals and their scan */
+int CountCall::level_partition(int l, LevelWork& w)
+{
+    const Level& V = lv[l];
+    HmPartNArgs a;
+    memset(&a, 0, sizeof(a));
+    a.parent = B[l - 1];
+    a.keys_in = (const uint32_t*)hand.keys;
+    a.in = hand.runs;
+    a.dbits = V.dbits;
+    a.restbits = w.restbits;
+    a.shard_bits = w.sb;
+    a.keys_out = w.kout;
+    a.nruns_out = w.nruns;
+    a.runs_out = w.runs_sh;
+    a.items = lv[l - 1].items;
+    a.seg = hand.seg;
+    if (timing) HIPCHK(hipEventRecord(ctx->ev[5 + 2 * (l - 1)], s));
+    if (w.contig) {
+        /* child totals, their scan, then the partition proper */
+        uint64_t *ptl, *ttl;
+        ENSURE(B_PARTIAL, 4096 * sizeof(uint64_t), ptl);
+        ENSURE(B_TOTAL, 4 * sizeof(uint64_t), ttl);
+        ENSURE(B_CTOT, V.nchildren * 8, a.ctot);
+        ENSURE(B_CBASE, V.nchildren * 8, a.cbase);
+        ENSURE(B_CCUR, V.nchildren * 4, a.ccur);
+        HIPCHK(hipMemsetAsync(a.ctot, 0, V.nchildren * 8, s));
+        HIPCHK(hipMemsetAsync(a.ccur, 0, V.nchildren * 4, s));
+        a.mode = HM_PN_HIST;
+        a.cbase_off = hot_mid ? (uint32_t)w.l1_total : 0u;
+        hm_launch_partition_hist(s, a);
+        hm_launch_scan(s, (const uint64_t*)a.ctot, V.nchildren, ptl, (uint64_t*)a.cbase, ttl + 3);
+        a.mode = HM_PN_CONTIG;
+    }
+    hm_launch_partN(s, a, lv[l - 1].items, V.out16, hand.seg != nullptr);
+    HIPCHK(hipGetLastError());
+    if (timing) HIPCHK(hipEventRecord(ctx->ev[6 + 2 * (l - 1)], s));
+    npart = l;
+    return HM_OK;
+}
+
+/* run scan: sharded counters -> flat child-ordered runs + key prefix, with
+ * the hot tiles hooked in as children of their level */
+int CountCall::level_runscan(int l, LevelWork& w)
+{
+    const Level& V = lv[l];
+    HmRsArgs& ra = w.ra;
+    memset(&ra, 0, sizeof(ra));
+    ra.nchildren = V.nchildren;
+    ra.dbits = V.dbits;
+    ra.shard_bits = w.sb;
+    ra.nruns = w.nruns;
+    ra.runs = w.runs_sh;
+    ra.parent_item_begin = hand.parent_item_begin;
+    ra.item_keys = (l == L - 1) ? ta : HM_TN;
+    ra.sparse_max = (l == L - 1) ? HM_SP_MAX : 0u;
+    uint64_t *partial, *tot;
+    ENSURE(B_SHOFF, (V.nchildren << w.sb) * sizeof(uint32_t), ra.shoff);
+    ENSURE(B_NR, V.nchildren * sizeof(uint64_t), ra.nr);
+    uint64_t* runbase;
+    ENSURE(B_RUNBASE0 + l, V.nchildren * sizeof(uint64_t), runbase);
+    ra.runbase = runbase;
+    ENSURE(B_PARTIAL, 4096 * sizeof(uint64_t), partial);
+    tot = ltot();
+    hm_launch_rs_count(s, ra);
+    /* hot tiles are children of the last level: of their z5 bucket at
+     * level 2, of their zs[1] ancestor (kept as a bucket, below) at level 3 */
+    const bool hot_level = nhot && l == (hot_mid ? 1 : L - 1);
+    if (hot_level) {
+        hr.dbits = V.dbits;
+        hr.nr = ra.nr;
+        hr.zp = zs[l - 1];
+        hr.c2b = (l == 2 && w.hot3) ? (const uint32_t*)ctx->bufs[B_C2B].p : nullptr;
+        hm_launch_hot_nr(s, hr);
+    }
+    /* a 3-level plan with hot tiles: each hot tile's zs[1] ancestor must be
+     * a level-2 bucket (its parent at level 3) even without cold keys */
+    uint8_t* force = nullptr;
+    if (w.hot3 && l == 1) {
+        ENSURE(B_HOT_FORCE, V.nchildren, force);
+        HIPCHK(hipMemsetAsync(force, 0, V.nchildren, s));
+        hr.dbits = V.dbits;
+        hr.zp = zs[1];
+        hm_launch_hot_force(s, hr, force);
+    }
+    ra.force = force;
+    hm_launch_scan(s, ra.nr, V.nchildren, partial, runbase, tot + 0);
+    HIPCHK(hipGetLastError());
+    unsigned long long* down = ctx->host_state + 2 * ST_COUNT;
+    /* the flat run list is sized by a bound, its length stays on the
+     * device (tot[0]): at most one run per (parent item, child) and per
+     * key, plus the hot tiles' region shards */
+    uint64_t nflat = std::min<uint64_t>(hand.level_keys, (uint64_t)lv[l - 1].items << V.dbits) +
+                     (uint64_t)HM_MAX_HOT * HM_L1_SHARDS + 1;
+    ra.nflat_dev = tot + 0;
+    if (nflat * 24 > (8ull << 30)) {
+        /* a bound of more than 8 GiB of run buffers: read the count back */
+        HIPCHK(hipMemcpyAsync(down, tot, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        HIPCHK(hm_sync(s));
+        nflat = down[0];
+        ra.nflat_dev = nullptr;
+    }
+    ra.nflat = nflat;
+    uint2* flat;
+    uint64_t* excl;
+    ENSURE(hand.slot_k ? B_FLAT_B : B_FLAT_A, (nflat + 1) * sizeof(uint2), flat);
+    ENSURE(hand.slot_k ? B_EXCL_B : B_EXCL_A, (nflat + 1) * sizeof(uint64_t), excl);
+    ENSURE(B_CNT, (nflat + 1) * sizeof(uint64_t), ra.cnt);
+    ra.flat = flat;
+    ra.excl = excl;
+    ra.big = w.rs_big;
+    ra.nbig = ra.big + HM_RS_BIG_MAX;   /* zeroed with nruns */
+    ra.big_min = ctx->rs_big_min;
+    hm_launch_rs_copy(s, ra);
+    if (hot_level) {
+        hr.runbase = runbase;
+        hr.flat = flat;
+        hr.cnt = ra.cnt;
+        hm_launch_hot_runs(s, hr);
+    }
+    hm_launch_scan(s, ra.cnt, nflat, partial, excl, tot + 1, ra.nflat_dev);
+    ra.total_keys = tot + 1;
+    ENSURE(B_NKEYS, V.nchildren * sizeof(uint32_t), ra.nkeys);
+    ENSURE(B_KEYBASE, V.nchildren * sizeof(uint32_t), ra.keybase);
+    ENSURE(B_VALS, V.nchildren * sizeof(uint64_t), ra.vals);
+    ENSURE(B_PREFIX, V.nchildren * sizeof(uint64_t), w.prefix);
+    hm_launch_rs_keys(s, ra);
+    hm_launch_scan(s, ra.vals, V.nchildren, partial, w.prefix, tot + 2);
+    HIPCHK(hipGetLastError());
+    return HM_OK;
+}
+
+/* the non-empty children become B_l (k_compact); the level's one read-back
+ * brings its totals, then B_l and its items are published */
+int CountCall::level_compact(int l, LevelWork& w)
+{
+    Level& V = lv[l];
+    const HmRsArgs& ra = w.ra;
+    int st;
+    /* B_l arrays: sized by nchildren (upper bound of |B_l|) */
+    const uint64_t cap = V.nchildren + 1;
+    HmCompactArgs ca;
+    memset(&ca, 0, sizeof(ca));
+    if ((st = bucket_arrays(l, cap, ca.out))) return st;
+    uint32_t* child_begin;
+    ENSURE(B_CHILD0 + l, ((uint64_t)hand.nparents + 1) * 4, child_begin);
+    ca.nchildren = V.nchildren;
+    ca.nparents = hand.nparents;
+    ca.dbits = V.dbits;
+    ca.vals = ra.vals;
+    ca.prefix = w.prefix;
+    ca.total = ltot() + 2;
+    ca.nkeys = ra.nkeys;
+    ca.nr = ra.nr;
+    ca.runbase = ra.runbase;
+    ca.keybase = ra.keybase;
+    ca.parent_coord = hand.parent_coord;
+    ca.child_begin = child_begin;
+    if (w.hot3 && l == 1) ENSURE(B_C2B, V.nchildren * 4, ca.c2b);   /* child -> bucket, for level 3 */
+    if (l == L - 1) {
+        ENSURE(B_SLOTS, cap * 4, slots);
+        ENSURE(B_SLOTBKT, cap * 4, slot_bucket);
+        ca.slots = slots;
+        ca.nslots = ctx->state + ST_NSLOTS;
+        ca.slot_bucket = slot_bucket;
+    }
+    hm_launch_compact(s, ca);
+    HIPCHK(hipGetLastError());
+    if ((st = read_state(ctx))) return st;   /* the level's totals come with it (ST_LTOT) */
+    const uint64_t tot_h = ctx->host_state[ST_LTOT + 2];
+    V.count = (uint32_t)(tot_h >> 32);
+    V.items = (uint32_t)(tot_h & 0xFFFFFFFFull);
+    if (l == L - 1) nslots = (uint32_t)(ctx->host_state[ST_NSLOTS] & 0xFFFFFFFFull);
+    /* after a child-contiguous level every item of the next spans one run */
+    return publish(l, ca.out, HmRuns{ra.flat, ra.excl}, w.kout, ctx->host_state[ST_LTOT + 1],
+                   w.contig ? B_SEG2 : -1);
+}
+
+/* final aggregation over B_L */
+int CountCall::aggregate()
+{
     o.keys = keys_out;
     o.counts = counts_out;
     o.capacity = (uint64_t)capacity;
     o.cursor = ctx->state + ST_CURSOR;
     o.zmin = zmin;
-    o.zmax = zmax;
-    unsigned long long* totals[HM_MAX_LEVELS + 1];
+    o.zmax = Z;
     for (int l = 0; l < L; l++) ENSURE(B_TOT0 + l, ((uint64_t)lv[l].count + 1) * 8, totals[l]);
+    const int l = L - 1;
+    uint32_t* gslots = nullptr;
+    ENSURE(B_GSLOTS, (uint64_t)(nslots ? nslots : 1) * HM_AG_CELLS * 4, gslots);
+    uint64_t* sptot;
+    ENSURE(B_TOTAL, 4 * sizeof(uint64_t), sptot);   /* total, base, k_small_pairs' batch counter */
     {
-        const int l = L - 1;
-        uint32_t* gslots = nullptr;
-        ENSURE(B_GSLOTS, (uint64_t)(nslots ? nslots : 1) * HM_AG_CELLS * 4, gslots);
-        uint64_t* sptot;
-        ENSURE(B_TOTAL, 4 * sizeof(uint64_t), sptot);   /* total, base, k_small_pairs' batch counter */
-        {
-            HmFill zf;
-            zf.k = 0;
-            if (nslots) hm_fill_add(zf, gslots, 0, (size_t)nslots * HM_AG_CELLS * 4);
-            hm_fill_add(zf, totals[l], 0, ((size_t)lv[l].count + 1) * 8);
-            hm_fill_add(zf, sptot + 2, 0, 8);
-            hm_launch_fill(s, zf);
-        }
-        HmAggArgs a;
-        memset(&a, 0, sizeof(a));
-        a.B = B[l];
-        a.keys = (const uint16_t*)keys_cur;
-        a.in = runs_cur;
-        a.Z = Z;
-        a.lg = Z - zb;
-        a.totals = totals[l];
-        a.gslots = gslots;
-        a.slot_bucket = slot_bucket;
-        a.out = o;
-        a.items = lv[l].items;
-        a.nslots = nslots;
-        const uint64_t cnt = (uint64_t)lv[l].count + 1;
-        uint64_t *spcnt, *spoff, *partial;
-        ENSURE(B_VALS, cnt * 8, spcnt);
-        ENSURE(B_PREFIX, cnt * 8, spoff);
-        ENSURE(B_PARTIAL, 4096 * sizeof(uint64_t), partial);
-        ENSURE(B_SPCODES, (level_keys + 8) * 2, a.codes);
-        a.spcnt = spcnt;
-        a.spoff = spoff;
-        a.sptotal = sptot;
-        a.spbase = (unsigned long long*)(sptot + 1);
-        a.spq = (uint32_t*)(sptot + 2);
-        hm_launch_aggregate(s, a, lv[l].items, nslots);
-        hm_launch_small(s, a, partial);
-        HIPCHK(hipGetLastError());
+        HmFill zf;
+        zf.k = 0;
+        if (nslots) hm_fill_add(zf, gslots, 0, (size_t)nslots * HM_AG_CELLS * 4);
+        hm_fill_add(zf, totals[l], 0, ((size_t)lv[l].count + 1) * 8);
+        hm_fill_add(zf, sptot + 2, 0, 8);
+        hm_launch_fill(s, zf);
     }
-    if (timing) HIPCHK(hipEventRecord(ev[nev], s));
-    nev++;
-    /* pooling: level l children -> parents in B_{l-1} (root for l = 0) */
+    HmAggArgs a;
+    memset(&a, 0, sizeof(a));
+    a.B = B[l];
+    a.keys = (const uint16_t*)hand.keys;
+    a.in = hand.runs;
+    a.Z = Z;
+    a.lg = Z - zb;
+    a.totals = totals[l];
+    a.gslots = gslots;
+    a.slot_bucket = slot_bucket;
+    a.out = o;
+    a.items = lv[l].items;
+    a.nslots = nslots;
+    const uint64_t cnt = (uint64_t)lv[l].count + 1;
+    uint64_t *spcnt, *spoff, *partial;
+    ENSURE(B_VALS, cnt * 8, spcnt);
+    ENSURE(B_PREFIX, cnt * 8, spoff);
+    ENSURE(B_PARTIAL, 4096 * sizeof(uint64_t), partial);
+    ENSURE(B_SPCODES, (hand.level_keys + 8) * 2, a.codes);
+    a.spcnt = spcnt;
+    a.spoff = spoff;
+    a.sptotal = sptot;
+    a.spbase = (unsigned long long*)(sptot + 1);
+    a.spq = (uint32_t*)(sptot + 2);
+    hm_launch_aggregate(s, a, lv[l].items, nslots);
+    hm_launch_small(s, a, partial);
+    HIPCHK(hipGetLastError());
+    return HM_OK;
+}
+
+/* pooling: level l children -> parents in B_{l-1} (root for l = 0) */
+int CountCall::pool()
+{
     for (int l = L - 1; l >= 0; l--) {
         HmPoolArgs pa;
         memset(&pa, 0, sizeof(pa));
@@ -1503,8 +1697,14 @@ static int count_impl(hm_ctx* ctx, const double* lat, const double* lon, const i
         hm_launch_pool(s, pa, lv[l].nparents);
         HIPCHK(hipGetLastError());
     }
-    if (timing) HIPCHK(hipEventRecord(ev[nev], s));
-    nev++;
+    return HM_OK;
+}
+
+/* a stream's tail re-keyed, the call's last read-back, hm_last_stats, the
+ * cells outside the square and the capacity verdict */
+int CountCall::finish()
+{
+    int st;
     if (ctx->tail_keys) {
         hm_launch_stream_rekey_dev(s, ctx->tail_keys, ctx->state + ST_CURSOR, (uint64_t)capacity, ctx->tail_state,
                                    ctx->tail_cb);
@@ -1512,6 +1712,7 @@ static int count_impl(hm_ctx* ctx, const double* lat, const double* lon, const i
         ctx->tail_done = 1;
     }
     if ((st = read_state(ctx))) return st;
+    hipEvent_t* ev = ctx->ev;
     for (int i = 0; timing && i + 1 < nev; i++) {
         float ms = 0;
         (void)hipEventElapsedTime(&ms, ev[i], ev[i + 1]);
@@ -1541,23 +1742,45 @@ static int count_impl(hm_ctx* ctx, const double* lat, const double* lon, const i
     if (nc > (unsigned long long)capacity || xt > (uint64_t)xcapacity) return HM_E_CAPACITY;
     return HM_OK;
 }
+}  // namespace
+
+/* one attempt of hm_count / hm_count_tiles: the pipeline, or the general path
+ * when the pipeline's dense child space is too large */
+static int count_impl(hm_ctx* ctx, const double* lat, const double* lon, const int64_t* rows, const int64_t* cols,
+                      const uint8_t* keep, int64_t n, int zmin, int zmax, uint64_t* keys_out, uint64_t* counts_out,
+                      int64_t capacity, int64_t* n_out, int64_t* xcells_out, int64_t xcapacity, int64_t* nx_out)
+{
+    CountCall c{ctx, lat, lon, rows, cols, keep, n, zmin, zmax, keys_out, counts_out, capacity, n_out, xcells_out,
+                xcapacity, nx_out};
+    int st = c.run();
+    if (st == HM_FALLBACK)
+        st = count_fallback(ctx, lat, lon, rows, cols, keep, n, zmin, zmax, keys_out, counts_out, capacity, n_out,
+                            xcells_out, xcapacity, nx_out);
+    return st;
+}
+
+/* an entry point's attempts: a second one after an allocation failure, with
+ * the arena released (cached buffers of earlier calls may be what is missing) */
+template <class Attempt>
+static int retry_nomem(hm_ctx* ctx, Attempt attempt)
+{
+    int st = attempt();
+    if (st == HM_E_NOMEM) {
+        arena_release(ctx);
+        st = attempt();
+    }
+    return st;
+}
 
 extern "C" int hm_count(hm_ctx* ctx, const double* lat, const double* lon, const uint8_t* keep, int64_t n, int zmin,
                         int zmax, uint64_t* keys_out, uint64_t* counts_out, int64_t capacity, int64_t* n_out,
                         int64_t* xcells_out, int64_t xcapacity, int64_t* nx_out)
 {
     if (n > 0 && (!lat || !lon)) return HM_E_ARG;
-    int st = HM_OK;
-    for (int attempt = 0; attempt < 2; attempt++) {
-        st = count_impl(ctx, lat, lon, nullptr, nullptr, keep, n, zmin, zmax, keys_out, counts_out, capacity, n_out,
-                        xcells_out, xcapacity, nx_out);
-        if (st == HM_FALLBACK)
-            st = count_fallback(ctx, lat, lon, nullptr, nullptr, keep, n, zmin, zmax, keys_out, counts_out, capacity,
-                                n_out, xcells_out, xcapacity, nx_out);
-        if (st != HM_E_NOMEM) break;
-        arena_release(ctx);   /* cached buffers of earlier calls may be what is missing */
-    }
-    return st;
+    return retry_nomem(ctx, [=] {
+        return count_impl(ctx, lat, lon, nullptr, nullptr, keep, n, zmin, zmax, keys_out, counts_out, capacity, n_out,
+                          xcells_out, xcapacity, nx_out);
+    });
 }
 
 extern "C" int hm_count_tiles(hm_ctx* ctx, const int64_t* row, const int64_t* col, const uint8_t* keep, int64_t n,
@@ -1565,17 +1788,10 @@ extern "C" int hm_count_tiles(hm_ctx* ctx, const int64_t* row, const int64_t* co
                               int64_t* n_out, int64_t* xcells_out, int64_t xcapacity, int64_t* nx_out)
 {
     if (n > 0 && (!row || !col)) return HM_E_ARG;
-    int st = HM_OK;
-    for (int attempt = 0; attempt < 2; attempt++) {
-        st = count_impl(ctx, nullptr, nullptr, row, col, keep, n, zmin, zmax, keys_out, counts_out, capacity, n_out,
-                        xcells_out, xcapacity, nx_out);
-        if (st == HM_FALLBACK)
-            st = count_fallback(ctx, nullptr, nullptr, row, col, keep, n, zmin, zmax, keys_out, counts_out, capacity,
-                                n_out, xcells_out, xcapacity, nx_out);
-        if (st != HM_E_NOMEM) break;
-        arena_release(ctx);
-    }
-    return st;
+    return retry_nomem(ctx, [=] {
+        return count_impl(ctx, nullptr, nullptr, row, col, keep, n, zmin, zmax, keys_out, counts_out, capacity, n_out,
+                          xcells_out, xcapacity, nx_out);
+    });
 }
 
 static int grouped_impl(hm_ctx* ctx, const double* lat, const double* lon, const int64_t* rows, const int64_t* cols,
@@ -1629,12 +1845,9 @@ extern "C" int hm_count_grouped(hm_ctx* ctx, const double* lat, const double* lo
                                 int64_t capacity, int64_t* n_out)
 {
     if (n > 0 && (!lat || !lon)) return HM_E_ARG;
-    int st = grouped_impl(ctx, lat, lon, nullptr, nullptr, keep, group, n, zmin, zmax, cells_out, capacity, n_out);
-    if (st == HM_E_NOMEM) {
-        arena_release(ctx);
-        st = grouped_impl(ctx, lat, lon, nullptr, nullptr, keep, group, n, zmin, zmax, cells_out, capacity, n_out);
-    }
-    return st;
+    return retry_nomem(ctx, [=] {
+        return grouped_impl(ctx, lat, lon, nullptr, nullptr, keep, group, n, zmin, zmax, cells_out, capacity, n_out);
+    });
 }
 
 extern "C" int hm_count_grouped_packed(hm_ctx* ctx, const double* lat, const double* lon, const uint8_t* keep,
@@ -1642,14 +1855,10 @@ extern "C" int hm_count_grouped_packed(hm_ctx* ctx, const double* lat, const dou
                                        uint64_t* gcounts_out, int64_t capacity, int64_t* n_out)
 {
     if (n > 0 && (!lat || !lon)) return HM_E_ARG;
-    int st = grouped_impl(ctx, lat, lon, nullptr, nullptr, keep, group, n, zmin, zmax, nullptr, capacity, n_out,
-                          keys_out, gcounts_out);
-    if (st == HM_E_NOMEM) {
-        arena_release(ctx);
-        st = grouped_impl(ctx, lat, lon, nullptr, nullptr, keep, group, n, zmin, zmax, nullptr, capacity, n_out,
-                          keys_out, gcounts_out);
-    }
-    return st;
+    return retry_nomem(ctx, [=] {
+        return grouped_impl(ctx, lat, lon, nullptr, nullptr, keep, group, n, zmin, zmax, nullptr, capacity, n_out,
+                            keys_out, gcounts_out);
+    });
 }
 
 extern "C" int hm_count_grouped_packed_tiles(hm_ctx* ctx, const int64_t* row, const int64_t* col,
@@ -1658,14 +1867,10 @@ extern "C" int hm_count_grouped_packed_tiles(hm_ctx* ctx, const int64_t* row, co
                                              int64_t* n_out)
 {
     if (n > 0 && (!row || !col)) return HM_E_ARG;
-    int st = grouped_impl(ctx, nullptr, nullptr, row, col, keep, group, n, zmin, zmax, nullptr, capacity, n_out,
-                          keys_out, gcounts_out);
-    if (st == HM_E_NOMEM) {
-        arena_release(ctx);
-        st = grouped_impl(ctx, nullptr, nullptr, row, col, keep, group, n, zmin, zmax, nullptr, capacity, n_out,
-                          keys_out, gcounts_out);
-    }
-    return st;
+    return retry_nomem(ctx, [=] {
+        return grouped_impl(ctx, nullptr, nullptr, row, col, keep, group, n, zmin, zmax, nullptr, capacity, n_out,
+                            keys_out, gcounts_out);
+    });
 }
 
 extern "C" int hm_count_grouped_tiles(hm_ctx* ctx, const int64_t* row, const int64_t* col, const uint8_t* keep,
@@ -1673,12 +1878,9 @@ extern "C" int hm_count_grouped_tiles(hm_ctx* ctx, const int64_t* row, const int
                                       int64_t capacity, int64_t* n_out)
 {
     if (n > 0 && (!row || !col)) return HM_E_ARG;
-    int st = grouped_impl(ctx, nullptr, nullptr, row, col, keep, group, n, zmin, zmax, cells_out, capacity, n_out);
-    if (st == HM_E_NOMEM) {
-        arena_release(ctx);
-        st = grouped_impl(ctx, nullptr, nullptr, row, col, keep, group, n, zmin, zmax, cells_out, capacity, n_out);
-    }
-    return st;
+    return retry_nomem(ctx, [=] {
+        return grouped_impl(ctx, nullptr, nullptr, row, col, keep, group, n, zmin, zmax, cells_out, capacity, n_out);
+    });
 }
 
 /* ------------------------------------------------------------------------ */

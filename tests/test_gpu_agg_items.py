@@ -3,7 +3,7 @@
 Two parameters of the count pipeline depend on the size of the call and never
 take their production values at parity sizes:
 
-  keys per final-aggregation work item (hm_api.cpp count_impl: HM_TA = 262144,
+  keys per final-aggregation work item (hm_api.cpp CountCall::plan: HM_TA = 262144,
   halved down to HM_TA_MIN = 16384 until the call holds HM_TA_ITEMS = 128
   items' worth of points): 16384 below 4,194,304 points, 262144 from
   33,554,432.  It sets the items per bucket (k_level1_buckets, the run scan),
