@@ -9,6 +9,10 @@
  * counts) to size the next grid; everything else stays on the device.
  * The driver is CountCall: run() calls its phases in that order, and LevelOut
  * is what one level hands to the next.
+ *
+ * Also here: the general path's driver, the cell merges and routes, the
+ * formatters and the context-level rasters.  The streaming heatmap
+ * (hm_stream_*) is hm_stream_api.cpp; hm_ctx.h holds what the two share.
  */
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -19,22 +23,12 @@
 
 #include <algorithm>
 #include <chrono>
-#include <string>
-#include <thread>
-#include <unordered_map>
-#include <unordered_set>
 #include <vector>
 
-#include "../../include/heatmap_amd.h"
 #include "hm_genkey.h"
-#include "hm_pipeline.h"
+#include "hm_ctx.h"
 
 namespace {
-
-struct Buf {
-    void* p = nullptr;
-    size_t cap = 0;
-};
 
 struct Level {
     int zc;              /* child zoom z_l */
@@ -56,78 +50,12 @@ struct Level {
 #define HM_SPREAD_MIN_COLD 1e30
 #define HM_SPREAD_ZOOMS 3
 
-/* per-call stage events: [0..4] stage boundaries, [5..] pairs around the
- * level >= 2 partition launches */
-#define HM_NEV 12
-
-struct hm_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    std::vector<Buf> bufs;
-    unsigned long long* state = nullptr;      /* device: err, exotic count, slow, cursor, nslots, ... */
-    unsigned long long* host_state = nullptr; /* pinned mirror */
-    int last_levels = 0;                      /* partition levels of the last count (stats [7]) */
-    uint32_t* host_aux = nullptr;             /* pinned: level-1 histogram / region sizes */
-    int64_t last_err_index = -1;
-    int last_err_kind = 0;
-    int64_t last_slow = 0;
-    double stage_us[9] = {0};              /* [8]: keys per aggregation work item (0: general path) */
-    hipEvent_t ev[HM_NEV];
-    /* plan-tuning knobs, read once from the environment at hm_ctx_create
-     * (INTEGRATION.md): HM_SPREAD_MIN_KEYS, HM_RS_BIG_MIN */
-    double spread_min_keys = 0;
-    double spread_min_cold = 0;
-    int sample_log2 = 18;              /* level-1 region sizing: ~2^sample_log2 sampled points */
-    int debug_l1 = 0;                  /* HM_DEBUG_L1: report level-1 region overflows on stderr */
-    int stage_timing = 1;              /* HM_STAGE_TIMING=0: no stage events (hm_last_stats stages read 0) */
-    int contig = 1;                    /* HM_CONTIG=0: 3-level plans keep run-streaming at the last level */
-    uint32_t ta_min = 16384;           /* HM_TA_MIN: smallest aggregation work item (keys) */
-    uint32_t ta_items = 128;           /* HM_TA_ITEMS: items' worth of points a call must have before ta halves */
-    /* a stream's tail cells: the count re-keys them under the batch's bucket
-     * (read on the device from the stream state) before its last read-back */
-    uint64_t* tail_keys = nullptr;
-    const unsigned long long* tail_state = nullptr;
-    int tail_cb = 0;
-    int tail_done = 0;
-    uint64_t rs_big_min = 0;
-    /* hot tiles (hm_pipeline.h): HM_HOT=0 turns them off; a tile is hot with
-     * >= 1/hot_inv_share of the sampled points and >= hot_min_keys estimated */
-    int hot = 1;
-    int hot_mid = 1;               /* HM_HOT_MID=0: no hot tiles in 3-level plans (zmax 19-21) */
-    double hot_inv_share = 4096;   /* 2048 -> 4096: 291 -> 470 hot tiles on the bench cloud, -0.13 ms */
-    double hot_min_keys = 65536;
-    int run_shard_bits = -1;   /* HM_RUN_SHARD_BITS: level >= 2 run-counter shards (-1: by plan) */
-};
-
-enum {
-    ST_ERR = 0,
-    ST_XCOUNT = 1,
-    ST_SLOW = 2,
-    ST_CURSOR = 3,
-    ST_NSLOTS = 4,
-    ST_REDO = 5,
-    ST_REDO_OUT = 6,
-    ST_XCURSOR = 7,
-    ST_OVERFLOW = 8,
-    ST_NHOT = 9,          /* hot tiles of this call (k_hot_select; low 32 bits) */
-    ST_L1TOTAL = 10,      /* level-1 regions' total capacity (k_l1_sizes) */
-    ST_LTOT = 12,         /* 12..14: a partition level's run, key and bucket totals (its run scans),
-                           * read back with the state in one copy */
-    ST_COUNT = 16
-};
-
-static int hip_fail(hipError_t e, const char* what)
+int hip_fail(hipError_t e, const char* what)
 {
     if (e == hipSuccess) return HM_OK;
     fprintf(stderr, "heatmap_amd: HIP error in %s: %s\n", what, hipGetErrorString(e));
     return HM_E_HIP;
 }
-
-#define HIPCHK(x)                                  \
-    do {                                           \
-        int _st = hip_fail((x), #x);               \
-        if (_st != HM_OK) return _st;              \
-    } while (0)
 
 /* Wait for the stream.  HM_SYNC_SPIN_US > 0 (environment, read once per
  * process): poll it for up to that long first, then block.  (Measured with a
@@ -141,7 +69,7 @@ static int hm_spin_us()
     }();
     return us;
 }
-static hipError_t hm_sync(hipStream_t s)
+hipError_t hm_sync(hipStream_t s)
 {
     const int spin = hm_spin_us();
     if (spin > 0) {
@@ -155,29 +83,7 @@ static hipError_t hm_sync(hipStream_t s)
     return hipStreamSynchronize(s);
 }
 
-/* named arena slots */
-enum {
-    B_KEYS_A, B_KEYS_B, B_RUNS_SH, B_FLAT_A, B_FLAT_B, B_EXCL_A, B_EXCL_B, B_CNT, B_SHOFF, B_NR, B_NRUNS,
-    B_NKEYS, B_KEYBASE, B_VALS, B_PREFIX, B_PARTIAL, B_TOTAL, B_ROOT, B_REDO_IDX, B_REDO_ROWS, B_REDO_COLS,
-    B_RUNBASE0,
-    B_BK0 = B_RUNBASE0 + HM_MAX_LEVELS, /* 4 levels x 8 arrays */
-    B_CHILD0 = B_BK0 + HM_MAX_LEVELS * 8,
-    B_TOT0 = B_CHILD0 + HM_MAX_LEVELS,
-    B_SLOTS = B_TOT0 + HM_MAX_LEVELS + 1,
-    B_SLOTBKT, B_GSLOTS, B_SPCODES, B_DESC0,
-    /* exotic list and the general path (hm_general.hip) */
-    B_X_ROW = B_DESC0 + HM_MAX_LEVELS, B_X_COL, B_X_IDX, B_GEN_KA, B_GEN_KB, B_GEN_FLAG, B_GEN_IDX, B_GEN_C,
-    B_GEN_KHA, B_GEN_KHB, B_GEN_HIST, B_GEN_ORAND, B_GL_GRP,
-    B_L1_FILL, B_L1_RBASE, B_L1_RCAP, B_L1_HIST, B_L1_SMASK,
-    B_RT_CNT, B_RT_OFF, B_MG_TABLE, B_MG_STATE, B_SEG, B_RS_BIG,
-    B_HOT, B_HOT_COUNTS, B_HOT_PARENT, B_D2B, B_MB_CNT, B_MB_OFF, B_MB_KEYS, B_MB_COUNTS, B_MB_CNT2, B_MB_OFF2,
-    B_MB_KEYS2, B_MB_COUNTS2, B_KEYS_C, B_HOT_FORCE, B_C2B, B_SEG2, B_CTOT, B_CBASE, B_CCUR, B_MG_PIECES,
-    B_L1_SLOT,
-    B_RS_B, B_RS_MX,   /* hm_raster_render: blurred counts, the two maxima */
-    B_COUNT
-};
-
-static int ensure(hm_ctx* c, int slot, size_t bytes, void** out)
+int ensure(hm_ctx* c, int slot, size_t bytes, void** out)
 {
     if (bytes == 0) bytes = 16;
     Buf& b = c->bufs[slot];
@@ -200,7 +106,7 @@ static int ensure(hm_ctx* c, int slot, size_t bytes, void** out)
 /* the arena is a cache: after an allocation failure every buffer is
  * released at the API boundary (nothing of the failed call is in flight
  * past the synchronisation) so the next call starts from an empty arena */
-static void arena_release(hm_ctx* c)
+void arena_release(hm_ctx* c)
 {
     (void)hipStreamSynchronize(c->stream);
     for (auto& b : c->bufs) {
@@ -210,14 +116,6 @@ static void arena_release(hm_ctx* c)
     }
     (void)hipGetLastError();
 }
-
-#define ENSURE(slot, bytes, ptr)                                         \
-    do {                                                                 \
-        void* _p = nullptr;                                              \
-        int _st = ensure(ctx, (slot), (size_t)(bytes), &_p);             \
-        if (_st != HM_OK) return _st;                                    \
-        ptr = (decltype(ptr))_p;                                         \
-    } while (0)
 
 extern "C" {
 
@@ -362,26 +260,6 @@ int hm_ctx_tune(hm_ctx* c, const char* name, double value, double* old)
     return HM_OK;
 }
 
-/* the plan-tuning fields of one context copied to another (a stream's helper
- * contexts count with the settings of the stream's own) */
-static void ctx_copy_tuning(hm_ctx* d, const hm_ctx* c)
-{
-    d->spread_min_keys = c->spread_min_keys;
-    d->spread_min_cold = c->spread_min_cold;
-    d->sample_log2 = c->sample_log2;
-    d->debug_l1 = c->debug_l1;
-    d->stage_timing = c->stage_timing;
-    d->contig = c->contig;
-    d->ta_min = c->ta_min;
-    d->ta_items = c->ta_items;
-    d->rs_big_min = c->rs_big_min;
-    d->hot = c->hot;
-    d->hot_mid = c->hot_mid;
-    d->hot_inv_share = c->hot_inv_share;
-    d->hot_min_keys = c->hot_min_keys;
-    d->run_shard_bits = c->run_shard_bits;
-}
-
 int hm_ctx_destroy(hm_ctx* c)
 {
     if (!c) return HM_OK;
@@ -415,6 +293,26 @@ int hm_last_stats(hm_ctx* c, int64_t* slow_points, double* stage_us, int n_stage
 }
 
 }  // extern "C"
+
+/* the plan-tuning fields of one context copied to another (a stream's helper
+ * contexts count with the settings of the stream's own) */
+void ctx_copy_tuning(hm_ctx* d, const hm_ctx* c)
+{
+    d->spread_min_keys = c->spread_min_keys;
+    d->spread_min_cold = c->spread_min_cold;
+    d->sample_log2 = c->sample_log2;
+    d->debug_l1 = c->debug_l1;
+    d->stage_timing = c->stage_timing;
+    d->contig = c->contig;
+    d->ta_min = c->ta_min;
+    d->ta_items = c->ta_items;
+    d->rs_big_min = c->rs_big_min;
+    d->hot = c->hot;
+    d->hot_mid = c->hot_mid;
+    d->hot_inv_share = c->hot_inv_share;
+    d->hot_min_keys = c->hot_min_keys;
+    d->run_shard_bits = c->run_shard_bits;
+}
 
 static int reset_state(hm_ctx* ctx)
 {
@@ -637,8 +535,6 @@ static int gen_count(hm_ctx* ctx, const int64_t* row, const int64_t* col, const 
     *total = down[0];
     return HM_OK;
 }
-
-#define HM_FALLBACK (-1)   /* CountCall: the pipeline's dense child space is too large */
 
 /* hm_count for data too sparse for the pipeline's dense per-level child
  * arrays (e.g. uniform clouds at zoom 21): every kept point through the
@@ -1794,9 +1690,9 @@ extern "C" int hm_count_tiles(hm_ctx* ctx, const int64_t* row, const int64_t* co
     });
 }
 
-static int grouped_impl(hm_ctx* ctx, const double* lat, const double* lon, const int64_t* rows, const int64_t* cols,
-                        const uint8_t* keep, const uint32_t* group, int64_t n, int zmin, int zmax, int64_t* cells_out,
-                        int64_t capacity, int64_t* n_out, uint64_t* pkeys = nullptr, uint64_t* pcounts = nullptr)
+int grouped_impl(hm_ctx* ctx, const double* lat, const double* lon, const int64_t* rows, const int64_t* cols,
+                 const uint8_t* keep, const uint32_t* group, int64_t n, int zmin, int zmax, int64_t* cells_out,
+                 int64_t capacity, int64_t* n_out, uint64_t* pkeys, uint64_t* pcounts)
 {
     const bool packed = pkeys || pcounts;
     if (!ctx || !n_out || n < 0 || n >= (int64_t)0xFFFFFFF0ll || zmin < 0 || zmax < zmin ||
@@ -1954,9 +1850,8 @@ extern "C" int hm_cells_route(hm_ctx* ctx, const uint64_t* keys, const uint64_t*
     return (layout != HM_CELLS_U64 && h[m + 1]) ? HM_E_WIDE : HM_OK;
 }
 
-static int cells_merge(hm_ctx* ctx, const void* keys_in, const void* counts_in, int layout, int64_t n,
-                       const int64_t* runs, int nruns, uint64_t* keys_out, uint64_t* counts_out, int64_t capacity,
-                       int64_t* n_out)
+int cells_merge(hm_ctx* ctx, const void* keys_in, const void* counts_in, int layout, int64_t n, const int64_t* runs,
+                int nruns, uint64_t* keys_out, uint64_t* counts_out, int64_t capacity, int64_t* n_out)
 {
     const uint16_t* recs = layout == HM_CELLS_REC10 ? (const uint16_t*)keys_in : nullptr;
     const uint64_t* keys = recs ? nullptr : (const uint64_t*)keys_in;
@@ -2433,919 +2328,11 @@ extern "C" int hm_bench_read(hm_ctx* ctx, const void* a, const void* b, int64_t 
     return HM_OK;
 }
 
-/* ------------------------------------------------------------------------ */
-/* streaming: resident multi-zoom heatmap (kernels in hm_stream.hip)          */
-/* ------------------------------------------------------------------------ */
-
-#define HMS_PAR 4
-struct hm_stream {
-    hm_ctx* ctx = nullptr;
-    int zmin = 0, zmax = 0;
-    int cb = 0;                           /* cell bits of a log key */
-    uint32_t base = 0;
-    unsigned long long* state = nullptr;  /* device HMS_ST_* words */
-    HmsBuckets bk{};                      /* (group, period) buckets */
-    uint64_t* bk_alt = nullptr;           /* hm_stream_expire: the fresh table the survivors' buckets move to */
-    uint32_t *bflag = nullptr, *blist = nullptr, *bloc = nullptr; /* per bucket: last batch, list, run */
-    uint32_t epoch = 0;
-    uint32_t last_nparts = 1;             /* buckets of the previous batch (1: count the next one speculatively) */
-    /* the cell log: llen cells of lcap; alt: the compaction target */
-    uint64_t *lkeys = nullptr, *lcounts = nullptr, *akeys = nullptr, *acounts = nullptr;
-    uint64_t lcap = 0, llen = 0;
-    bool compact = true;                  /* the log holds distinct keys */
-    bool par = true;                      /* several-bucket batches counted concurrently (HM_STREAM_PAR=0: not) */
-    /* while compact: the buckets with cells in the log.  A one-bucket batch
-     * of a bucket not in it keeps the log compact (one count's cells are
-     * distinct), so a stream of new hours never needs a compaction pass */
-    std::unordered_set<uint32_t> log_buckets;
-    uint64_t nbuckets = 0;
-    unsigned long long* hstate = nullptr; /* pinned mirror of state */
-    Buf bids, rec;                        /* per-batch scratch */
-    Buf plat, plon, pkeep, pstart, pcnt;  /* partition path: bucket-contiguous batch */
-    int64_t rcap = 0;                     /* records rec holds */
-    Buf rk, rc, mk, mc;                   /* rollup scratch: relabeled and merged cells */
-    /* several-bucket batches: up to HMS_PAR buckets counted at once, each by
-     * its own context, stream and host thread, into its own scratch */
-    hm_ctx* pctx[HMS_PAR] = {};
-    Buf pk[HMS_PAR], pc[HMS_PAR];
-    hipEvent_t pev = nullptr;
-    /* the log arrays as growable reservations (log_alloc): base -> its
-     * reservation, so a full log maps more pages behind its cells instead of
-     * being copied into a buffer twice the size */
-    struct VArr {
-        size_t reserved = 0, mapped = 0;
-        std::vector<std::pair<hipMemGenericAllocationHandle_t, size_t>> chunks;
-    };
-    std::unordered_map<void*, VArr> varr;
-    bool vmm = true;                      /* HM_STREAM_VMM=0: plain allocations, grown by copying */
-    /* maps the log's next extent ahead of need, on a host thread, while the
-     * batches run (every varr access joins it first) */
-    std::thread premap;
-};
-
-static void premap_join(hm_stream* s)
-{
-    if (s->premap.joinable()) s->premap.join();
-}
-
-/* ---- the log's growable arrays ---- */
-static hipMemAllocationProp log_prop(int device)
-{
-    hipMemAllocationProp prop = {};
-    prop.type = hipMemAllocationTypePinned;
-    prop.location.type = hipMemLocationTypeDevice;
-    prop.location.id = device;
-    return prop;
-}
-
-/* map [mapped, bytes) of reservation v at base p (bytes: a granularity multiple) */
-static bool log_map(hm_stream* s, void* p, hm_stream::VArr& v, size_t bytes)
-{
-    if (bytes <= v.mapped) return true;
-    if (bytes > v.reserved) return false;
-    const hipMemAllocationProp prop = log_prop(s->ctx->device);
-    const size_t add = bytes - v.mapped;
-    hipMemGenericAllocationHandle_t h;
-    if (hipMemCreate(&h, add, &prop, 0) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    char* at = (char*)p + v.mapped;
-    hipMemAccessDesc d = {};
-    d.location = prop.location;
-    d.flags = hipMemAccessFlagsProtReadWrite;
-    if (hipMemMap(at, add, 0, h, 0) != hipSuccess) {
-        (void)hipGetLastError();
-        (void)hipMemRelease(h);
-        return false;
-    }
-    if (hipMemSetAccess(at, add, &d, 1) != hipSuccess) {
-        (void)hipGetLastError();
-        (void)hipMemUnmap(at, add);
-        (void)hipMemRelease(h);
-        return false;
-    }
-    v.chunks.push_back({h, add});
-    v.mapped = bytes;
-    return true;
-}
-
-static size_t log_round(hm_stream* s, size_t bytes)
-{
-    const hipMemAllocationProp prop = log_prop(s->ctx->device);
-    size_t g = 0;
-    if (hipMemGetAllocationGranularity(&g, &prop, hipMemAllocationGranularityRecommended) != hipSuccess || !g) {
-        (void)hipGetLastError();
-        g = 2u << 20;
-    }
-    return (bytes + g - 1) / g * g;
-}
-
-static void log_free(hm_stream* s, void* p)
-{
-    premap_join(s);
-    if (!p) return;
-    auto it = s->varr.find(p);
-    if (it == s->varr.end()) {
-        (void)hipFree(p);
-        return;
-    }
-    size_t off = 0;
-    for (auto& c : it->second.chunks) {
-        (void)hipMemUnmap((char*)p + off, c.second);
-        (void)hipMemRelease(c.first);
-        off += c.second;
-    }
-    (void)hipMemAddressFree(p, it->second.reserved);
-    s->varr.erase(it);
-}
-
-/* n cells: a reservation of 64x that (at most the device's memory) with the
- * first n mapped, or a plain allocation when reservations are off or fail */
-static int log_alloc(hm_stream* s, uint64_t n, uint64_t** out)
-{
-    premap_join(s);
-    *out = nullptr;
-    if (s->vmm) {
-        size_t total = 0, freeb = 0;
-        if (hipMemGetInfo(&freeb, &total) != hipSuccess) {
-            (void)hipGetLastError();
-            total = 0;
-        }
-        const size_t want = log_round(s, (size_t)n * 8);
-        size_t res = log_round(s, std::max<size_t>(want, std::min<size_t>((size_t)n * 8 * 64, total ? total : want)));
-        void* p = nullptr;
-        if (hipMemAddressReserve(&p, res, 0, nullptr, 0) == hipSuccess) {
-            hm_stream::VArr v;
-            v.reserved = res;
-            if (log_map(s, p, v, want)) {
-                s->varr[p] = std::move(v);
-                *out = (uint64_t*)p;
-                return HM_OK;
-            }
-            (void)hipMemAddressFree(p, res);
-        }
-        (void)hipGetLastError();
-    }
-    if (hipMalloc((void**)out, n * 8) != hipSuccess) {
-        (void)hipGetLastError();
-        *out = nullptr;
-        return HM_E_NOMEM;
-    }
-    return HM_OK;
-}
-
-/* grow the array at p to n cells in place; false: not a reservation, or it is too small */
-static bool log_grow(hm_stream* s, uint64_t* p, uint64_t n)
-{
-    premap_join(s);
-    auto it = s->varr.find((void*)p);
-    return it != s->varr.end() && log_map(s, p, it->second, log_round(s, (size_t)n * 8));
-}
-
-static int stream_sync_state(hm_stream* s)
-{
-    HIPCHK(hipMemcpyAsync(s->hstate, s->state, HMS_ST_COUNT * sizeof(unsigned long long), hipMemcpyDeviceToHost,
-                          s->ctx->stream));
-    HIPCHK(hm_sync(s->ctx->stream));
-    s->nbuckets = s->hstate[HMS_ST_BUCKETS];
-    return HM_OK;
-}
-
-static int stream_buf(hm_stream* s, Buf& b, size_t bytes)
-{
-    (void)s;
-    if (b.cap >= bytes) return HM_OK;
-    if (b.p) HIPCHK(hipFree(b.p));
-    b.p = nullptr;
-    b.cap = 0;
-    if (hipMalloc(&b.p, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        return HM_E_NOMEM;
-    }
-    b.cap = bytes;
-    return HM_OK;
-}
-
-static int stream_alloc2(hm_stream* s, uint64_t n, uint64_t** k, uint64_t** c)
-{
-    *k = nullptr;
-    *c = nullptr;
-    if (log_alloc(s, n, k) != HM_OK || log_alloc(s, n, c) != HM_OK) {
-        log_free(s, *k);
-        *k = nullptr;
-        *c = nullptr;
-        return HM_E_NOMEM;
-    }
-    return HM_OK;
-}
-
-/* sum the log's equal keys (the bucketed LDS merge) into the alternate
- * arrays, then swap them in */
-static int stream_compact(hm_stream* s)
-{
-    if (s->compact || s->llen == 0) {
-        s->compact = true;
-        return HM_OK;
-    }
-    int st;
-    if (!s->akeys && (st = stream_alloc2(s, s->lcap, &s->akeys, &s->acounts))) return st;
-    int64_t m = 0;
-    if ((st = cells_merge(s->ctx, s->lkeys, s->lcounts, HM_CELLS_U64, (int64_t)s->llen, nullptr, 0, s->akeys, s->acounts,
-                          (int64_t)s->lcap, &m)))
-        return st;
-    std::swap(s->lkeys, s->akeys);
-    std::swap(s->lcounts, s->acounts);
-    s->llen = (uint64_t)m;
-    s->compact = true;   /* (compaction adds no bucket: log_buckets stays exact) */
-    return HM_OK;
-}
-
-/* room for `need` more cells at the log's tail: compact first, then grow */
-/* the log will be over 3/4 full: map the next doubling's pages now, on a
- * host thread (hipMemCreate of a few hundred MB costs about a batch) */
-static void premap_ahead(hm_stream* s, uint64_t need)
-{
-    if (!s->vmm || s->premap.joinable() || s->lcap - s->llen - need >= s->lcap / 4) return;
-    auto ik = s->varr.find((void*)s->lkeys), ic = s->varr.find((void*)s->lcounts);
-    if (ik == s->varr.end() || ic == s->varr.end()) return;
-    const size_t bytes = log_round(s, (size_t)s->lcap * 16);
-    if (bytes > ik->second.reserved || bytes > ic->second.reserved) return;
-    if (ik->second.mapped >= bytes && ic->second.mapped >= bytes) return;
-    hm_stream::VArr *vk = &ik->second, *vc = &ic->second;   /* (stable: every insert or erase joins first) */
-    void *pk = s->lkeys, *pc = s->lcounts;
-    const int dev = s->ctx->device;
-    s->premap = std::thread([s, vk, vc, pk, pc, bytes, dev]() {
-        (void)hipSetDevice(dev);
-        if (log_map(s, pk, *vk, bytes)) (void)log_map(s, pc, *vc, bytes);
-    });
-}
-
-static int stream_room(hm_stream* s, uint64_t need)
-{
-    if (s->lcap - s->llen >= need) {
-        premap_ahead(s, need);
-        return HM_OK;
-    }
-    premap_join(s);
-    int st;
-    if ((st = stream_compact(s))) return st;
-    if (s->lcap - s->llen >= need) return HM_OK;
-    uint64_t cap = s->lcap ? s->lcap : 1024;
-    while (cap - s->llen < need) cap <<= 1;
-    /* reservations: more pages behind the cells, no copy and no sync (the
-     * compaction target, when there is one, grows with them or is dropped) */
-    if (log_grow(s, s->lkeys, cap) && log_grow(s, s->lcounts, cap)) {
-        if (s->akeys && !(log_grow(s, s->akeys, cap) && log_grow(s, s->acounts, cap))) {
-            HIPCHK(hm_sync(s->ctx->stream));
-            log_free(s, s->akeys);
-            log_free(s, s->acounts);
-            s->akeys = s->acounts = nullptr;
-        }
-        s->lcap = cap;
-        return HM_OK;
-    }
-    uint64_t *k, *c;
-    if ((st = stream_alloc2(s, cap, &k, &c))) return st;
-    hipStream_t q = s->ctx->stream;
-    if (s->llen) {
-        HIPCHK(hipMemcpyAsync(k, s->lkeys, s->llen * 8, hipMemcpyDeviceToDevice, q));
-        HIPCHK(hipMemcpyAsync(c, s->lcounts, s->llen * 8, hipMemcpyDeviceToDevice, q));
-    }
-    HIPCHK(hm_sync(q));
-    for (uint64_t* p : {s->lkeys, s->lcounts, s->akeys, s->acounts}) log_free(s, p);
-    s->lkeys = k;
-    s->lcounts = c;
-    s->akeys = s->acounts = nullptr;   /* the compaction target, at the new size when needed */
-    s->lcap = cap;
-    return HM_OK;
-}
-
-/* m cells appended at the tail; bucket: the batch's one bucket, or
- * 0xFFFFFFFF for cells of several buckets (from then on the log's buckets
- * are not all known, and every append clears the compact flag) */
-static void stream_appended(hm_stream* s, uint64_t m, const uint32_t* buckets, uint32_t nb)
-{
-    if (m) {
-        /* each bucket's cells come from one count, so they are distinct: the
-         * log stays compact when it was empty, or when none of the buckets
-         * has cells in it yet (the log's buckets all known) */
-        if (s->llen == 0) s->log_buckets.clear();
-        bool fresh = !s->log_buckets.count(0xFFFFFFFFu);
-        for (uint32_t j = 0; j < nb && fresh; j++) fresh = !s->log_buckets.count(buckets[j]);
-        s->compact = s->compact && (s->llen == 0 || fresh);
-        for (uint32_t j = 0; j < nb; j++) s->log_buckets.insert(buckets[j]);
-    }
-    s->llen += m;
-}
-
-static void stream_appended(hm_stream* s, uint64_t m, uint32_t bucket = 0xFFFFFFFFu)
-{
-    stream_appended(s, m, &bucket, 1);
-}
-
-/* a batch of one bucket, part 1: hm_count's cells written at the log's tail
- * (not yet part of the log) */
-static int stream_count_tail(hm_stream* s, const double* lat, const double* lon, const uint8_t* keep, int64_t n,
-                             int64_t* m)
-{
-    int st;
-    *m = 0;
-    if ((st = stream_room(s, 2 * (uint64_t)n + 1024))) return st; /* typical batches: fewer cells than 2 per point */
-    for (;;) {
-        int64_t nx = 0;
-        s->ctx->tail_keys = s->lkeys + s->llen;
-        s->ctx->tail_state = s->state;
-        s->ctx->tail_cb = s->cb;
-        s->ctx->tail_done = 0;
-        st = hm_count(s->ctx, lat, lon, keep, n, s->zmin, s->zmax, s->lkeys + s->llen, s->lcounts + s->llen,
-                      (int64_t)(s->lcap - s->llen), m, nullptr, 0, &nx);
-        s->ctx->tail_keys = nullptr;
-        /* the log's keys hold tiles inside [0, 2^z)^2 only */
-        if (nx > 0) return HM_E_EXOTIC;
-        if (st != HM_E_CAPACITY) return st;
-        if ((st = stream_room(s, (uint64_t)(*m + *m / 4 + 1024)))) return st;
-    }
-}
-
-/* part 2: the tail's m cells keyed under the bucket and appended */
-static int stream_take_tail(hm_stream* s, int64_t m, uint32_t bucket)
-{
-    /* re-keyed inside the count already unless it took the fallback path */
-    if (!s->ctx->tail_done)
-        hm_launch_stream_rekey(s->ctx->stream, s->lkeys + s->llen, (uint64_t)m, (uint64_t)bucket << s->cb);
-    HIPCHK(hipGetLastError());
-    stream_appended(s, (uint64_t)m, bucket);
-    return HM_OK;
-}
-
-/* a batch of several buckets: one grouped pass with the bucket as group */
-static int stream_fold_grouped(hm_stream* s, const double* lat, const double* lon, const uint8_t* keep, int64_t n)
-{
-    int64_t m = 0;
-    int st;
-    if (s->rcap < 2 * n + 1024) {
-        const int64_t want = 2 * n + 1024;
-        if ((st = stream_buf(s, s->rec, (size_t)want * 40))) return st;
-        s->rcap = want;
-    }
-    for (;;) {
-        st = grouped_impl(s->ctx, lat, lon, nullptr, nullptr, keep, (const uint32_t*)s->bids.p, n, s->zmin, s->zmax,
-                          (int64_t*)s->rec.p, s->rcap, &m);
-        if (st != HM_E_CAPACITY) break;
-        const int64_t want = m + m / 4 + 1024;
-        if ((st = stream_buf(s, s->rec, (size_t)want * 40))) return st;
-        s->rcap = want;
-    }
-    if (st) return st;
-    if ((st = stream_room(s, (uint64_t)m + 1))) return st;
-    hipStream_t q = s->ctx->stream;
-    HIPCHK(hipMemsetAsync(s->state + HMS_ST_EXOTIC, 0, 8, q));
-    hm_launch_stream_convert(q, (const int64_t*)s->rec.p, (uint64_t)m, s->cb, s->lkeys + s->llen,
-                             s->lcounts + s->llen, s->state);
-    HIPCHK(hipGetLastError());
-    if ((st = stream_sync_state(s))) return st;
-    if (s->hstate[HMS_ST_EXOTIC]) return HM_E_EXOTIC;   /* checked before the cells join the log */
-    stream_appended(s, (uint64_t)m);
-    return HM_OK;
-}
-
-/* The several-bucket batch's runs (gathered by stream_fold_parts, the
- * points not kept last; at most HMS_PAR runs in all) counted at once, each by
- * its own context, HIP stream and host thread into its own scratch, then
- * copied to the log's tail in bucket order and keyed -- nothing joins the
- * log unless every run counted.  HM_FALLBACK: a run failed (the caller's
- * sequential path re-counts and reports the batch's first failing point). */
-static int stream_fold_parts_par(hm_stream* s, const double* lat, const double* lon, const uint8_t* keep, int64_t n,
-                                 uint32_t nparts, const std::vector<uint64_t>& start, const std::vector<uint32_t>& hb)
-{
-    hm_ctx* ctx = s->ctx;
-    hipStream_t q = ctx->stream;
-    int st;
-    for (int t = 0; t < HMS_PAR; t++) {
-        if (s->pctx[t]) continue;
-        hipStream_t pq = nullptr;
-        HIPCHK(hipStreamCreateWithFlags(&pq, hipStreamNonBlocking));
-        if ((st = hm_ctx_create(&s->pctx[t], ctx->device, pq))) {
-            (void)hipStreamDestroy(pq);
-            return st;
-        }
-    }
-    for (int t = 0; t < HMS_PAR; t++) ctx_copy_tuning(s->pctx[t], ctx);   /* hm_ctx_tune of the stream's context */
-    if (!s->pev) HIPCHK(hipEventCreateWithFlags(&s->pev, hipEventDisableTiming));
-    HIPCHK(hipEventRecord(s->pev, q));   /* the gathered runs are written */
-    const uint32_t nall = nparts + 1;    /* + the points not kept (errors only) */
-    std::vector<int64_t> m(nall, 0);
-    std::vector<int> rc(nall, HM_OK);
-    for (uint32_t j0 = 0; j0 < nall; j0 += HMS_PAR) {
-        const uint32_t j1 = std::min<uint32_t>(nall, j0 + HMS_PAR);
-        std::vector<std::thread> th;
-        for (uint32_t j = j0; j < j1; j++) {
-            const int t = (int)(j - j0);
-            th.emplace_back([&, j, t]() {
-                hm_ctx* c = s->pctx[t];
-                (void)hipSetDevice(c->device);
-                const uint64_t nj = (j < nparts ? start[j + 1] : (uint64_t)n) - start[j];
-                if (!nj) return;
-                if (hipStreamWaitEvent(c->stream, s->pev, 0) != hipSuccess) {
-                    rc[j] = HM_E_HIP;
-                    return;
-                }
-                const double* la = (const double*)s->plat.p + start[j];
-                const double* lo = (const double*)s->plon.p + start[j];
-                const uint8_t* kp = j < nparts ? nullptr : (const uint8_t*)s->pkeep.p;
-                uint64_t cap = j < nparts ? 2 * nj + 1024 : 0;
-                for (;;) {
-                    if (cap && stream_buf(s, s->pk[t], cap * 8) != HM_OK) {
-                        rc[j] = HM_E_NOMEM;
-                        return;
-                    }
-                    if (cap && stream_buf(s, s->pc[t], cap * 8) != HM_OK) {
-                        rc[j] = HM_E_NOMEM;
-                        return;
-                    }
-                    int64_t mj = 0, nx = 0;
-                    const int r = hm_count(c, la, lo, kp, (int64_t)nj, s->zmin, s->zmax,
-                                           cap ? (uint64_t*)s->pk[t].p : nullptr, cap ? (uint64_t*)s->pc[t].p : nullptr,
-                                           (int64_t)cap, &mj, nullptr, 0, &nx);
-                    if (nx > 0) {
-                        rc[j] = HM_E_EXOTIC;
-                        return;
-                    }
-                    if (r == HM_E_CAPACITY && j < nparts) {
-                        cap = (uint64_t)mj + (uint64_t)mj / 4 + 1024;
-                        continue;
-                    }
-                    rc[j] = (r == HM_E_CAPACITY) ? HM_OK : r;   /* the unkept part has no cells */
-                    m[j] = mj;
-                    return;
-                }
-            });
-        }
-        for (auto& x : th) x.join();
-        for (uint32_t j = j0; j < j1; j++)
-            if (rc[j] == HM_E_EXOTIC) return HM_E_EXOTIC;
-        for (uint32_t j = j0; j < j1; j++)
-            if (rc[j] != HM_OK) return HM_FALLBACK;
-        /* this group's cells to the tail, in bucket order */
-        uint64_t need = 0;
-        for (uint32_t j = j0; j < j1 && j < nparts; j++) need += (uint64_t)m[j];
-        if ((st = stream_room(s, need + 1024))) return st;
-        for (uint32_t j = j0; j < j1 && j < nparts; j++) {
-            const int t = (int)(j - j0);
-            if (!m[j]) continue;
-            uint64_t* tk = s->lkeys + s->llen;
-            HIPCHK(hipMemcpyAsync(tk, s->pk[t].p, (size_t)m[j] * 8, hipMemcpyDeviceToDevice, q));
-            HIPCHK(hipMemcpyAsync(s->lcounts + s->llen, s->pc[t].p, (size_t)m[j] * 8, hipMemcpyDeviceToDevice, q));
-            hm_launch_stream_rekey(q, tk, (uint64_t)m[j], (uint64_t)hb[j] << s->cb);
-            HIPCHK(hipGetLastError());
-            stream_appended(s, (uint64_t)m[j], &hb[j], 1);
-        }
-    }
-    return HM_OK;
-}
-
-/* a batch of a few buckets: gathered into one run per bucket (+ one run of
- * the points not kept), one hm_count per run written at the log's tail, all
- * counted before the tail joins the log.  Errors: the batch is re-counted as
- * a whole so the reported point is the first failing one in input order, as
- * hm_count's. */
-static int stream_fold_parts(hm_stream* s, const double* lat, const double* lon, const uint8_t* keep, int64_t n,
-                             uint32_t nparts)
-{
-    hm_ctx* ctx = s->ctx;
-    hipStream_t q = ctx->stream;
-    int st;
-    std::vector<uint32_t> hb(nparts);
-    std::vector<uint64_t> start(2 * (nparts + 2), 0);   /* starts | run sizes, then cursors */
-    if ((st = stream_buf(s, s->pstart, (size_t)(nparts + 2) * 16))) return st;
-    uint64_t* dstart = (uint64_t*)s->pstart.p;
-    HmsScatterArgs a;
-    a.lat = lat;
-    a.lon = lon;
-    a.keep = keep;
-    a.bids = (const uint32_t*)s->bids.p;
-    a.loc = s->bloc;
-    a.n = (uint64_t)n;
-    a.nparts = nparts;
-    a.start = dstart;
-    a.cursor = (unsigned long long*)(dstart + nparts + 2);
-    hm_launch_stream_batch_list(q, s->blist, nparts, s->bloc);
-    HIPCHK(hipMemsetAsync(a.cursor, 0, (size_t)(nparts + 2) * 8, q));
-    hm_launch_stream_part_count(q, a);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(hb.data(), s->blist, nparts * 4, hipMemcpyDeviceToHost, q));
-    HIPCHK(hipMemcpyAsync(start.data() + nparts + 2, a.cursor, (size_t)(nparts + 1) * 8, hipMemcpyDeviceToHost, q));
-    HIPCHK(hm_sync(q));
-    uint64_t kept = 0;
-    for (uint32_t j = 0; j < nparts; j++) {
-        start[j] = kept;
-        kept += start[nparts + 2 + j];
-    }
-    start[nparts] = kept;
-    start[nparts + 1] = (uint64_t)n;
-    if (kept + start[2 * nparts + 2] != (uint64_t)n) return HM_E_HIP;   /* cannot happen */
-    if ((st = stream_buf(s, s->plat, (size_t)n * 8)) || (st = stream_buf(s, s->plon, (size_t)n * 8))) return st;
-    HIPCHK(hipMemcpyAsync(dstart, start.data(), (size_t)(nparts + 2) * 8, hipMemcpyHostToDevice, q));
-    HIPCHK(hipMemsetAsync(a.cursor, 0, (size_t)(nparts + 2) * 8, q));
-    a.lat_out = (double*)s->plat.p;
-    a.lon_out = (double*)s->plon.p;
-    hm_launch_stream_scatter(q, a);
-    HIPCHK(hipGetLastError());
-    const uint64_t nun = (uint64_t)n - kept;
-    if (nun) {
-        if ((st = stream_buf(s, s->pkeep, (size_t)nun))) return st;
-        HIPCHK(hipMemsetAsync(s->pkeep.p, 0, nun, q));
-    }
-    if (nparts >= 2 && nparts + 1 <= HMS_PAR && s->par) {   /* one group: the batch stays atomic */
-        st = stream_fold_parts_par(s, lat, lon, keep, n, nparts, start, hb);
-        if (st != HM_FALLBACK) return st;
-    }
-    if ((st = stream_room(s, 2 * kept + 1024))) return st;
-    for (;;) {
-        uint64_t off = 0;
-        bool grow = false;
-        for (uint32_t j = 0; j <= nparts && !grow; j++) {
-            const uint64_t nj = (j < nparts ? start[j + 1] : (uint64_t)n) - start[j];
-            if (!nj) continue;
-            int64_t m = 0, nx = 0;
-            uint64_t* tk = s->lkeys + s->llen + off;
-            uint64_t* tc = s->lcounts + s->llen + off;
-            st = hm_count(ctx, (const double*)s->plat.p + start[j], (const double*)s->plon.p + start[j],
-                          j < nparts ? nullptr : (const uint8_t*)s->pkeep.p, (int64_t)nj, s->zmin, s->zmax, tk, tc,
-                          (int64_t)(s->lcap - s->llen - off), &m, nullptr, 0, &nx);
-            /* the log's keys hold tiles inside [0, 2^z)^2 only (and with no
-             * record buffer given, hm_count reports them as capacity) */
-            if (nx > 0) return HM_E_EXOTIC;
-            if (st == HM_E_CAPACITY) {
-                if ((st = stream_room(s, (off + (uint64_t)m) * 5 / 4 + 1024))) return st;
-                grow = true;
-                break;
-            }
-            if (st != HM_OK) {
-                /* the first failing point in input order */
-                int64_t m2 = 0, nx2 = 0;
-                const int st2 = hm_count(ctx, lat, lon, keep, n, s->zmin, s->zmax, nullptr, nullptr, 0, &m2, nullptr,
-                                         0, &nx2);
-                return st2 != HM_OK && st2 != HM_E_CAPACITY ? st2 : st;
-            }
-            if (j < nparts) {
-                hm_launch_stream_rekey(q, tk, (uint64_t)m, (uint64_t)hb[j] << s->cb);
-                HIPCHK(hipGetLastError());
-                off += (uint64_t)m;
-            }
-        }
-        if (grow) continue;
-        /* several buckets' cells, each bucket's from one count */
-        stream_appended(s, off, hb.data(), nparts);
-        return HM_OK;
-    }
-}
-
-extern "C" int hm_stream_create(hm_ctx* ctx, int zmin, int zmax, uint32_t base_hour, int64_t initial_cells,
-                                int64_t max_buckets, hm_stream** out)
-{
-    if (!ctx || !out || zmin < 0 || zmax < zmin || zmax > HM_MAX_ZOOM || initial_cells < 0 || max_buckets < 0)
-        return HM_E_ARG;
-    *out = nullptr;
-    HIPCHK(hipSetDevice(ctx->device));
-    hm_stream* s = new hm_stream();
-    s->ctx = ctx;
-    s->zmin = zmin;
-    s->zmax = zmax;
-    s->base = base_hour;
-    /* cell bits: the pyramid index of zooms 0..zmax, (4^(zmax+1) - 1)/3 values */
-    const uint64_t ncell = ((1ull << (2 * (zmax + 1))) - 1) / 3;
-    while ((1ull << s->cb) < ncell) s->cb++;
-    const int bb = 64 - s->cb;   /* bucket bits: 21 at zmax 21 */
-    uint64_t nb = 1024;
-    const uint64_t want = max_buckets ? (uint64_t)max_buckets : (1ull << 20);
-    while (nb < want + want / 4 && nb < (1ull << bb)) nb <<= 1;
-    s->bk.mask = nb - 1;
-    s->lcap = std::max<uint64_t>(1024, (uint64_t)initial_cells);
-    if (const char* e = getenv("HM_STREAM_PAR")) s->par = atoi(e) != 0;
-    if (const char* e = getenv("HM_STREAM_VMM")) s->vmm = atoi(e) != 0;
-    int st = HM_OK;
-    if (hipMalloc((void**)&s->state, HMS_ST_COUNT * sizeof(unsigned long long)) != hipSuccess ||
-        hipHostMalloc((void**)&s->hstate, 2 * HMS_ST_COUNT * sizeof(unsigned long long)) != hipSuccess ||
-        hipMalloc((void**)&s->bk.keys, nb * 8) != hipSuccess || hipMalloc((void**)&s->bflag, nb * 4) != hipSuccess ||
-        hipMalloc((void**)&s->blist, nb * 4) != hipSuccess || hipMalloc((void**)&s->bloc, nb * 4) != hipSuccess ||
-        stream_alloc2(s, s->lcap, &s->lkeys, &s->lcounts) != HM_OK) {
-        (void)hipGetLastError();
-        hm_stream_destroy(s);
-        return HM_E_NOMEM;
-    }
-    st = hip_fail(hipMemsetAsync(s->state, 0, HMS_ST_COUNT * sizeof(unsigned long long), ctx->stream), "memset");
-    if (st == HM_OK) {
-        hm_launch_stream_fill(ctx->stream, s->bk.keys, nb, HMS_EMPTY);
-        st = hip_fail(hipGetLastError(), "fill");
-        if (st == HM_OK) st = hip_fail(hipMemsetAsync(s->bflag, 0, nb * 4, ctx->stream), "memset");
-    }
-    if (st == HM_OK) st = stream_sync_state(s);
-    if (st) {
-        hm_stream_destroy(s);
-        return st;
-    }
-    *out = s;
-    return HM_OK;
-}
-
-extern "C" int hm_stream_add(hm_stream* s, const double* lat, const double* lon, const uint8_t* keep,
-                             const uint32_t* hour, const uint32_t* group, int64_t n)
-{
-    if (!s || n < 0 || (n > 0 && (!lat || !lon)) || n >= (int64_t)0xFFFFFFF0ll) return HM_E_ARG;
-    hm_ctx* ctx = s->ctx;
-    /* hm_last_error is this call's: a batch of a few buckets is counted on
-     * helper contexts and would leave an earlier call's error standing */
-    ctx->last_err_index = -1;
-    ctx->last_err_kind = HM_OK;
-    if (n == 0) return HM_OK;
-    HIPCHK(hipSetDevice(ctx->device));
-    hipStream_t q = ctx->stream;
-    int st;
-    /* buckets of the kept points (interned; a failing batch may leave unused
-     * buckets behind, never cells) */
-    /* reset BFULL, EXOTIC, BMM, NLIST, ERR in one copy */
-    unsigned long long* init = s->hstate + HMS_ST_COUNT;
-    init[0] = 0;                                    /* BFULL */
-    init[1] = 0;                                    /* EXOTIC */
-    init[2] = 0;                                    /* BMM */
-    init[3] = 0;                                    /* NLIST */
-    init[4] = ~0ull;                                /* ERR */
-    HIPCHK(hipMemcpyAsync(s->state + HMS_ST_BFULL, init, 5 * 8, hipMemcpyHostToDevice, q));
-    const bool per_point = group || hour;
-    if (per_point && (st = stream_buf(s, s->bids, (size_t)n * 4))) return st;
-    HmsBucketArgs a;
-    a.group = group;
-    a.hour = hour;
-    a.keep = per_point ? keep : nullptr;
-    a.n = per_point ? (uint64_t)n : 1;   /* neither: the one (no group, undated) bucket */
-    a.base = s->base;
-    a.buckets = s->bk;
-    /* per-point bucket ids feed only the several-bucket paths: a batch
-     * counted speculatively as one bucket skips writing them (and a batch
-     * that turns out to hold several runs the pass again, below) */
-    const bool spec = s->last_nparts <= 1;   /* the previous batch was one bucket */
-    a.out = per_point && !spec ? (uint32_t*)s->bids.p : nullptr;
-    if (++s->epoch == 0) s->epoch = 1;   /* wrapped: stale flags only cost an exchange */
-    a.bflag = s->bflag;
-    a.epoch = s->epoch;
-    a.list = s->blist;
-    a.state = s->state;
-    a.err_word = s->state + HMS_ST_ERR;
-    hm_launch_stream_buckets(q, a);
-    hm_launch_stream_collect(q, s->bflag, s->bk.mask + 1, s->epoch, s->blist, s->state);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(s->hstate, s->state, HMS_ST_COUNT * sizeof(unsigned long long), hipMemcpyDeviceToHost, q));
-    /* the usual batch is one bucket: count it right away (into the log's
-     * tail); the bucket pass's state arrives with the count's first
-     * read-back.  Any other outcome drops the tail and takes the paths below
-     * (which count again, so errors and their order are the same). */
-    int64_t m1 = 0;
-    const int st1 = spec ? stream_count_tail(s, lat, lon, keep, n, &m1) : HM_OK;
-    HIPCHK(hm_sync(q));
-    s->nbuckets = s->hstate[HMS_ST_BUCKETS];
-    const uint32_t nparts = (uint32_t)s->hstate[HMS_ST_NLIST];
-    s->last_nparts = nparts;
-    const uint32_t lo = (uint32_t)s->hstate[HMS_ST_BMM];
-    const unsigned long long e = s->hstate[HMS_ST_ERR];
-    if (e != ~0ull) {
-        /* a kept point with a bad hour.  A point before it that does not
-         * project is the batch's first failing point (input order, as
-         * hm_count's).  Error path only, so the batch simply goes through one
-         * more whole hm_count with no room for cells: it ends in a point's
-         * error, or in HM_OK / HM_E_CAPACITY when every point projects (then
-         * the hour is the error).  A failure of that call itself (memory,
-         * HIP) is returned as it is. */
-        const int64_t hi = (int64_t)(e >> 8);
-        int64_t m2 = 0, nx2 = 0;
-        const int st2 = hm_count(ctx, lat, lon, keep, n, s->zmin, s->zmax, nullptr, nullptr, 0, &m2, nullptr, 0, &nx2);
-        const bool point = st2 == HM_E_NAN || st2 == HM_E_DOMAIN || st2 == HM_E_INF || st2 == HM_E_RANGE;
-        if (point && ctx->last_err_index >= 0 && ctx->last_err_index < hi) return st2;
-        if (!point && st2 != HM_OK && st2 != HM_E_CAPACITY) return st2;
-        ctx->last_err_index = hi;
-        ctx->last_err_kind = (int)(e & 0xFF);
-        return ctx->last_err_kind;
-    }
-    if (s->hstate[HMS_ST_BFULL]) return HM_E_CAPACITY;   /* max_buckets (group, hour) pairs */
-    if (nparts <= 1) { /* one bucket (the usual time-ordered batch), or nothing kept */
-        if (!spec && (st = stream_count_tail(s, lat, lon, keep, n, &m1))) return st;
-        if (spec && st1) return st1;
-        return stream_take_tail(s, m1, nparts ? lo : 0u);
-    }
-    if (spec && per_point) {
-        /* the ids the speculative pass skipped (the buckets are interned and
-         * listed already: the same epoch, nothing new to flag) */
-        a.out = (uint32_t*)s->bids.p;
-        hm_launch_stream_buckets(q, a);
-        HIPCHK(hipGetLastError());
-    }
-    if (nparts <= HMS_MAX_PARTS) return stream_fold_parts(s, lat, lon, keep, n, nparts);
-    return stream_fold_grouped(s, lat, lon, keep, n);
-}
-
-extern "C" int hm_stream_cells(hm_stream* s, int64_t* cells, int64_t* capacity, int64_t* buckets)
-{
-    if (!s) return HM_E_ARG;
-    HIPCHK(hipSetDevice(s->ctx->device));
-    int st;
-    if (cells) {
-        /* distinct (bucket, cell) pairs: the log compacted */
-        if ((st = stream_compact(s))) return st;
-        *cells = (int64_t)s->llen;
-    }
-    if (capacity) *capacity = (int64_t)s->lcap;
-    if (buckets) {
-        if ((st = stream_sync_state(s))) return st;
-        *buckets = (int64_t)s->nbuckets;
-    }
-    return HM_OK;
-}
-
-/* the tail of every query: the filter pass's read-back, then the label cells
- * in the scratch arrays (HMS_ST_CURSOR of them) merged and emitted */
-static int stream_merge_emit(hm_stream* s, uint64_t* keys_out, uint64_t* counts_out, uint32_t* groups_out,
-                             uint32_t* periods_out, int64_t capacity, int64_t* n_out)
-{
-    hm_ctx* ctx = s->ctx;
-    hipStream_t q = ctx->stream;
-    int st;
-    if ((st = stream_sync_state(s))) return st;
-    if (s->hstate[HMS_ST_BFULL]) return HM_E_CAPACITY;   /* no bucket left for a rollup label */
-    const uint64_t m = s->hstate[HMS_ST_CURSOR];
-    if (m == 0) return HM_OK;
-    /* equal label cells summed */
-    if ((st = stream_buf(s, s->mk, m * 8)) || (st = stream_buf(s, s->mc, m * 8))) return st;
-    int64_t nd = 0;
-    if ((st = cells_merge(ctx, (const uint64_t*)s->rk.p, (const uint64_t*)s->rc.p, HM_CELLS_U64, (int64_t)m, nullptr, 0,
-                          (uint64_t*)s->mk.p, (uint64_t*)s->mc.p, (int64_t)m, &nd)))
-        return st;
-    *n_out = nd;
-    if (nd > capacity) return HM_E_CAPACITY;
-    HmsEmitArgs e;
-    e.keys = (const uint64_t*)s->mk.p;
-    e.counts = (const uint64_t*)s->mc.p;
-    e.n = (uint64_t)nd;
-    e.buckets = s->bk;
-    e.cb = s->cb;
-    e.zmin = s->zmin;
-    e.zmax = s->zmax;
-    e.base = s->base;
-    e.keys_out = keys_out;
-    e.counts_out = counts_out;
-    e.groups_out = groups_out;
-    e.periods_out = periods_out;
-    hm_launch_stream_emit(q, e);
-    HIPCHK(hipGetLastError());
-    return HM_OK;
-}
-
-/* a rollup's three passes: relabel, merge, emit (span: HM_SPAN_*, or
- * HMS_SPAN_WINDOW with the hour offsets [lo, hi)) */
-static int stream_rollup(hm_stream* s, int span, int merge_groups, int64_t select, uint32_t lo, uint32_t hi,
-                         uint64_t* keys_out, uint64_t* counts_out, uint32_t* groups_out, uint32_t* periods_out,
-                         int64_t capacity, int64_t* n_out)
-{
-    *n_out = 0;
-    hm_ctx* ctx = s->ctx;
-    HIPCHK(hipSetDevice(ctx->device));
-    hipStream_t q = ctx->stream;
-    int st;
-    if (s->llen == 0) return HM_OK;
-    /* the log's cells of the rollup, re-keyed to label buckets */
-    if ((st = stream_buf(s, s->rk, s->llen * 8)) || (st = stream_buf(s, s->rc, s->llen * 8))) return st;
-    unsigned long long* cur = s->state + HMS_ST_CURSOR;
-    HIPCHK(hipMemsetAsync(cur, 0, 8, q));
-    HIPCHK(hipMemsetAsync(s->state + HMS_ST_BFULL, 0, 8, q));
-    HmsRelabelArgs a;
-    a.keys = s->lkeys;
-    a.counts = s->lcounts;
-    a.n = s->llen;
-    a.buckets = s->bk;
-    a.cb = s->cb;
-    a.span = span;
-    a.merge = merge_groups ? 1 : 0;
-    a.base = s->base;
-    a.select = select;
-    a.lo = lo;
-    a.hi = hi;
-    a.keys_out = (uint64_t*)s->rk.p;
-    a.counts_out = (uint64_t*)s->rc.p;
-    a.cursor = cur;
-    a.state = s->state;
-    hm_launch_stream_relabel(q, a);
-    HIPCHK(hipGetLastError());
-    return stream_merge_emit(s, keys_out, counts_out, groups_out, periods_out, capacity, n_out);
-}
-
-extern "C" int hm_stream_rollup(hm_stream* s, int span, int merge_groups, int64_t select, uint64_t* keys_out,
-                                uint64_t* counts_out, uint32_t* groups_out, uint32_t* periods_out, int64_t capacity,
-                                int64_t* n_out)
-{
-    if (!s || !n_out || span < HM_SPAN_HOUR || span > HM_SPAN_ALLTIME || select < -1 || capacity < 0 ||
-        (capacity > 0 && (!keys_out || !counts_out)))
-        return HM_E_ARG;
-    return stream_rollup(s, span, merge_groups, select, 0, 0, keys_out, counts_out, groups_out, periods_out, capacity,
-                         n_out);
-}
-
-/* hour -> offset from the stream's base, clamped to [0, 2^28] */
-static uint32_t stream_hour_offset(const hm_stream* s, int64_t hour)
-{
-    const int64_t off = hour - (int64_t)s->base;
-    return (uint32_t)std::min<int64_t>(std::max<int64_t>(off, 0), (int64_t)HMS_MAX_HOUR_OFFSET);
-}
-
-extern "C" int hm_stream_window(hm_stream* s, int64_t hour_lo, int64_t hour_hi, int merge_groups, uint64_t* keys_out,
-                                uint64_t* counts_out, uint32_t* groups_out, int64_t capacity, int64_t* n_out)
-{
-    if (!s || !n_out || hour_hi <= hour_lo || capacity < 0 || (capacity > 0 && (!keys_out || !counts_out)))
-        return HM_E_ARG;
-    *n_out = 0;
-    const uint32_t lo = stream_hour_offset(s, hour_lo), hi = stream_hour_offset(s, hour_hi);
-    if (lo >= hi) return HM_OK;   /* all of it outside the stream's hours */
-    return stream_rollup(s, HMS_SPAN_WINDOW, merge_groups, -1, lo, hi, keys_out, counts_out, groups_out, nullptr,
-                         capacity, n_out);
-}
-
-/* a view's three passes: filter (k_stream_view, in place of the relabel),
- * then the rollup's merge and emit over the survivors only */
-static int stream_view(hm_stream* s, HmsViewArgs& a, uint64_t* keys_out, uint64_t* counts_out, uint32_t* groups_out,
-                       int64_t capacity, int64_t* n_out)
-{
-    hm_ctx* ctx = s->ctx;
-    HIPCHK(hipSetDevice(ctx->device));
-    hipStream_t q = ctx->stream;
-    int st;
-    if (s->llen == 0) return HM_OK;
-    if ((st = stream_buf(s, s->rk, s->llen * 8)) || (st = stream_buf(s, s->rc, s->llen * 8))) return st;
-    unsigned long long* cur = s->state + HMS_ST_CURSOR;
-    HIPCHK(hipMemsetAsync(cur, 0, 8, q));
-    HIPCHK(hipMemsetAsync(s->state + HMS_ST_BFULL, 0, 8, q));
-    a.keys = s->lkeys;
-    a.counts = s->lcounts;
-    a.n = s->llen;
-    a.buckets = s->bk;
-    a.cb = s->cb;
-    a.keys_out = (uint64_t*)s->rk.p;
-    a.counts_out = (uint64_t*)s->rc.p;
-    a.cursor = cur;
-    a.state = s->state;
-    hm_launch_stream_view(q, a);
-    HIPCHK(hipGetLastError());
-    return stream_merge_emit(s, keys_out, counts_out, groups_out, nullptr, capacity, n_out);
-}
-
-extern "C" int hm_stream_view(hm_stream* s, int64_t hour_lo, int64_t hour_hi, int64_t group, const int64_t* rects,
-                              int nrects, uint64_t* keys_out, uint64_t* counts_out, uint32_t* groups_out,
-                              int64_t capacity, int64_t* n_out)
-{
-    const bool alltime = hour_lo == HM_STREAM_ALLTIME && hour_hi == HM_STREAM_ALLTIME;
-    if (!s || !n_out || !rects || nrects < 1 || nrects > HM_VIEW_MAX_RECTS || (!alltime && hour_hi <= hour_lo) ||
-        group < HM_VIEW_EACH || group > (int64_t)HMS_NOGROUP || capacity < 0 ||
-        (capacity > 0 && (!keys_out || !counts_out)))
-        return HM_E_ARG;
-    *n_out = 0;
-    HmsViewArgs a;
-    a.nrects = 0;
-    uint64_t box_hi = 0;
-    a.box_lo = ~0ull;
-    for (int r = 0; r < nrects; r++) {
-        const int64_t z = rects[5 * r], side = 1ll << (z < 0 || z > HM_MAX_ZOOM ? 0 : z);
-        int64_t rlo = rects[5 * r + 1], rhi = rects[5 * r + 2], clo = rects[5 * r + 3], chi = rects[5 * r + 4];
-        if (z < s->zmin || z > s->zmax || rhi <= rlo || chi <= clo) return HM_E_ARG;
-        /* clipped to the square; what is left may be nothing */
-        rlo = std::max<int64_t>(rlo, 0), clo = std::max<int64_t>(clo, 0);
-        rhi = std::min<int64_t>(rhi, side), chi = std::min<int64_t>(chi, side);
-        if (rhi <= rlo || chi <= clo) continue;
-        HmsViewRect& R = a.rects[a.nrects++];
-        R.id_lo = ((1ull << (2 * z)) - 1ull) / 3ull + ((uint64_t)rlo << z);
-        R.span = (uint64_t)(rhi - rlo) << z;
-        R.cmask = (uint32_t)(side - 1);
-        R.col_lo = (uint32_t)clo;
-        R.col_w = (uint32_t)(chi - clo);
-        R.pad = 0;
-        a.box_lo = std::min(a.box_lo, R.id_lo);
-        box_hi = std::max(box_hi, R.id_lo + R.span);
-    }
-    if (a.nrects == 0) return HM_OK;   /* every rectangle outside the square */
-    a.box_span = box_hi - a.box_lo;
-    a.alltime = alltime ? 1 : 0;
-    a.lo = a.hi = 0;
-    if (!alltime) {
-        a.lo = stream_hour_offset(s, hour_lo), a.hi = stream_hour_offset(s, hour_hi);
-        if (a.lo >= a.hi) return HM_OK;   /* all of it outside the stream's hours */
-    }
-    a.gmode = group == HM_VIEW_MERGED ? HMS_VIEW_MERGED : (group == HM_VIEW_EACH ? HMS_VIEW_EACH : HMS_VIEW_GROUP);
-    a.group = group >= 0 ? (uint32_t)group : 0u;
-    return stream_view(s, a, keys_out, counts_out, groups_out, capacity, n_out);
-}
-
 /* ---- rasters: dense tile grids and rendered tiles (hm_raster.hip) ---- */
 
 /* the shared argument check of the two scatters: tiles inside their squares,
  * bin zooms inside [zlo, zhi] */
-static bool raster_args_ok(const int64_t* tiles, int ntiles, int bins_log2, int halo, int zlo, int zhi)
+bool raster_args_ok(const int64_t* tiles, int ntiles, int bins_log2, int halo, int zlo, int zhi)
 {
     if (!tiles || ntiles < 1 || ntiles > HM_RASTER_MAX_TILES || bins_log2 < 0 || bins_log2 > HM_RASTER_MAX_BINS_LOG2 ||
         halo < 0 || halo > HM_RASTER_MAX_HALO)
@@ -3356,63 +2343,6 @@ static bool raster_args_ok(const int64_t* tiles, int ntiles, int bins_log2, int 
         if (tr < 0 || tc < 0 || tr >= (1ll << tz) || tc >= (1ll << tz)) return false;
     }
     return true;
-}
-
-extern "C" int hm_stream_raster(hm_stream* s, int64_t hour_lo, int64_t hour_hi, int64_t group, const int64_t* tiles,
-                                int ntiles, int bins_log2, int halo, uint64_t* grid_out)
-{
-    const bool alltime = hour_lo == HM_STREAM_ALLTIME && hour_hi == HM_STREAM_ALLTIME;
-    if (!s || !grid_out || (!alltime && hour_hi <= hour_lo) || group < HM_VIEW_MERGED || group > (int64_t)HMS_NOGROUP ||
-        !raster_args_ok(tiles, ntiles, bins_log2, halo, s->zmin, s->zmax))
-        return HM_E_ARG;
-    hm_ctx* ctx = s->ctx;
-    HIPCHK(hipSetDevice(ctx->device));
-    hipStream_t q = ctx->stream;
-    const int64_t S = 1ll << bins_log2, W = S + 2 * halo;
-    HIPCHK(hipMemsetAsync(grid_out, 0, (size_t)ntiles * W * W * 8, q));
-    HmsRasterArgs a;
-    a.alltime = alltime ? 1 : 0;
-    a.lo = a.hi = 0;
-    if (!alltime) {
-        a.lo = stream_hour_offset(s, hour_lo), a.hi = stream_hour_offset(s, hour_hi);
-        if (a.lo >= a.hi) return HM_OK;   /* all of it outside the stream's hours */
-    }
-    if (s->llen == 0) return HM_OK;
-    uint64_t box_hi = 0;
-    a.box_lo = ~0ull;
-    for (int t = 0; t < ntiles; t++) {
-        const int64_t z = tiles[3 * t] + bins_log2, side = 1ll << z;
-        const int64_t oy = (tiles[3 * t + 1] << bins_log2) - halo, ox = (tiles[3 * t + 2] << bins_log2) - halo;
-        /* the haloed square clipped to [0, 2^z)^2: never empty, the tile itself is inside */
-        const int64_t rlo = std::max<int64_t>(oy, 0), rhi = std::min<int64_t>(oy + W, side);
-        const int64_t clo = std::max<int64_t>(ox, 0), chi = std::min<int64_t>(ox + W, side);
-        HmsRasterRect& R = a.rects[t];
-        R.id_lo = ((1ull << (2 * z)) - 1ull) / 3ull + ((uint64_t)rlo << z);
-        R.span = (uint64_t)(rhi - rlo) << z;
-        R.col_lo = (uint32_t)clo;
-        R.col_w = (uint32_t)(chi - clo);
-        R.z = (uint8_t)z;
-        R.y0 = (uint8_t)(rlo - oy);
-        R.x0 = (uint8_t)(clo - ox);
-        R.pad0 = 0;
-        R.pad = 0;
-        a.box_lo = std::min(a.box_lo, R.id_lo);
-        box_hi = std::max(box_hi, R.id_lo + R.span);
-    }
-    a.box_span = box_hi - a.box_lo;
-    a.keys = s->lkeys;
-    a.counts = s->lcounts;
-    a.n = s->llen;
-    a.buckets = s->bk;
-    a.cb = s->cb;
-    a.ntiles = ntiles;
-    a.gmode = group == HM_VIEW_MERGED ? HMS_VIEW_MERGED : HMS_VIEW_GROUP;
-    a.group = group >= 0 ? (uint32_t)group : 0u;
-    a.W = (uint32_t)W;
-    a.grid = (unsigned long long*)grid_out;
-    hm_launch_stream_raster(q, a);
-    HIPCHK(hipGetLastError());
-    return HM_OK;
 }
 
 extern "C" int hm_cells_raster(hm_ctx* ctx, const uint64_t* keys, const uint64_t* counts, int64_t n,
@@ -3478,222 +2408,5 @@ extern "C" int hm_raster_render(hm_ctx* ctx, const uint64_t* grid, int ntiles, i
     HIPCHK(hm_sync(q));
     if (down[0] >= wide) return HM_E_WIDE;
     if (vmax_used) *vmax_used = a.vs ? a.vs : (uint64_t)down[1];
-    return HM_OK;
-}
-
-extern "C" int hm_stream_expire(hm_stream* s, int64_t before_hour, int64_t* cells_dropped, int64_t* buckets_freed)
-{
-    if (!s) return HM_E_ARG;
-    if (cells_dropped) *cells_dropped = 0;
-    if (buckets_freed) *buckets_freed = 0;
-    const uint32_t cut = stream_hour_offset(s, before_hour);
-    if (cut == 0 || s->llen == 0) return HM_OK;   /* nothing is dated before the base hour */
-    hm_ctx* ctx = s->ctx;
-    HIPCHK(hipSetDevice(ctx->device));
-    hipStream_t q = ctx->stream;
-    int st;
-    premap_join(s);
-    const uint64_t nb = s->bk.mask + 1;
-    if (!s->akeys && (st = stream_alloc2(s, s->lcap, &s->akeys, &s->acounts))) return st;
-    if (!s->bk_alt && hipMalloc((void**)&s->bk_alt, nb * 8) != hipSuccess) {
-        (void)hipGetLastError();
-        s->bk_alt = nullptr;
-        return HM_E_NOMEM;
-    }
-    /* the survivors' buckets are counted into BUCKETS and listed (NLIST):
-     * the stream's own count comes back if nothing turns out to expire */
-    const uint64_t old_buckets = s->nbuckets;
-    unsigned long long* init = s->hstate + HMS_ST_COUNT;
-    for (int j = 0; j < HMS_ST_COUNT; j++) init[j] = 0;
-    /* CURSOR, BUCKETS, BFULL, EXOTIC, BMM, NLIST in one copy */
-    HIPCHK(hipMemcpyAsync(s->state + HMS_ST_CURSOR, init, (HMS_ST_NLIST - HMS_ST_CURSOR + 1) * 8,
-                          hipMemcpyHostToDevice, q));
-    hm_launch_stream_fill(q, s->bk_alt, nb, HMS_EMPTY);
-    HmsExpireArgs a;
-    a.keys = s->lkeys;
-    a.counts = s->lcounts;
-    a.n = s->llen;
-    a.old_buckets = s->bk;
-    a.new_buckets.keys = s->bk_alt;
-    a.new_buckets.mask = s->bk.mask;
-    a.cb = s->cb;
-    a.cut = cut;
-    a.keys_out = s->akeys;
-    a.counts_out = s->acounts;
-    a.cursor = s->state + HMS_ST_CURSOR;
-    a.state = s->state;
-    hm_launch_stream_expire(q, a);
-    hm_launch_stream_occupied(q, a.new_buckets, s->blist, s->state + HMS_ST_NLIST);
-    HIPCHK(hipGetLastError());
-    /* log_buckets holds old slot ids: it is rebuilt from the new table's
-     * occupied slots, read back as a list (every one has cells in the log;
-     * there are no more of them than the old table's buckets) */
-    std::vector<uint32_t> slots((size_t)std::min<uint64_t>(old_buckets, nb));
-    if (!slots.empty())
-        HIPCHK(hipMemcpyAsync(slots.data(), s->blist, slots.size() * 4, hipMemcpyDeviceToHost, q));
-    st = stream_sync_state(s);
-    const uint64_t kept = s->hstate[HMS_ST_CURSOR], nslots = s->hstate[HMS_ST_NLIST];
-    const bool bad = st || s->hstate[HMS_ST_BFULL] || kept > s->llen || nslots != s->nbuckets || nslots > slots.size();
-    if (bad || kept == s->llen) {
-        /* nothing expired (or, cannot happen, the pass failed): the stream stays as it is */
-        s->nbuckets = old_buckets;
-        init[0] = old_buckets;
-        HIPCHK(hipMemcpyAsync(s->state + HMS_ST_BUCKETS, init, 8, hipMemcpyHostToDevice, q));
-        HIPCHK(hm_sync(q));
-        return st ? st : (bad ? HM_E_HIP : HM_OK);
-    }
-    std::swap(s->lkeys, s->akeys);
-    std::swap(s->lcounts, s->acounts);
-    std::swap(s->bk.keys, s->bk_alt);
-    if (cells_dropped) *cells_dropped = (int64_t)(s->llen - kept);
-    if (buckets_freed) *buckets_freed = (int64_t)(old_buckets - s->nbuckets);
-    s->llen = kept;
-    /* a filter of distinct keys stays distinct: a compact log stays compact */
-    if (kept == 0) s->compact = true;
-    s->log_buckets.clear();
-    s->log_buckets.insert(slots.begin(), slots.begin() + (size_t)nslots);
-    /* slot ids changed: no bucket is flagged by an earlier batch */
-    HIPCHK(hipMemsetAsync(s->bflag, 0, nb * 4, q));
-    s->last_nparts = 1;
-    return HM_OK;
-}
-
-/* the whole log, compacted, in one pass (k_stream_export): the log's buckets
- * are raw, so a cell's bucket key is its group and hour (no relabel, no merge) */
-extern "C" int hm_stream_export(hm_stream* s, uint64_t* keys_out, uint64_t* counts_out, uint32_t* groups_out,
-                                uint32_t* hours_out, int64_t capacity, int64_t* n_out)
-{
-    if (!s || !n_out || capacity < 0 || (capacity > 0 && (!keys_out || !counts_out))) return HM_E_ARG;
-    *n_out = 0;
-    HIPCHK(hipSetDevice(s->ctx->device));
-    int st;
-    if ((st = stream_compact(s))) return st;
-    *n_out = (int64_t)s->llen;
-    if (s->llen == 0) return HM_OK;
-    if ((int64_t)s->llen > capacity) return HM_E_CAPACITY;
-    HmsEmitArgs e;
-    e.keys = s->lkeys;
-    e.counts = s->lcounts;
-    e.n = s->llen;
-    e.buckets = s->bk;
-    e.cb = s->cb;
-    e.zmin = s->zmin;
-    e.zmax = s->zmax;
-    e.base = s->base;
-    e.keys_out = keys_out;
-    e.counts_out = counts_out;
-    e.groups_out = groups_out;
-    e.periods_out = hours_out;
-    hm_launch_stream_export(s->ctx->stream, e);
-    HIPCHK(hipGetLastError());
-    return HM_OK;
-}
-
-/* pre-aggregated cells appended at the log's tail (k_stream_import), their
- * buckets listed as a batch's are; one state read-back, and the tail becomes
- * part of the log only when every cell was valid and found a bucket */
-extern "C" int hm_stream_import(hm_stream* s, const uint64_t* keys, const uint64_t* counts, const uint32_t* groups,
-                                const uint32_t* hours, int64_t n, int flags)
-{
-    if (!s || n < 0 || (n > 0 && (!keys || !counts)) || (flags & ~HM_IMPORT_DISTINCT)) return HM_E_ARG;
-    hm_ctx* ctx = s->ctx;
-    ctx->last_err_index = -1;
-    ctx->last_err_kind = HM_OK;
-    if (n == 0) return HM_OK;
-    HIPCHK(hipSetDevice(ctx->device));
-    hipStream_t q = ctx->stream;
-    int st;
-    if ((st = stream_room(s, (uint64_t)n))) return st;
-    /* reset BFULL, EXOTIC, BMM, NLIST, ERR in one copy (as hm_stream_add) */
-    unsigned long long* init = s->hstate + HMS_ST_COUNT;
-    init[0] = init[1] = init[2] = init[3] = 0;
-    init[4] = ~0ull;
-    HIPCHK(hipMemcpyAsync(s->state + HMS_ST_BFULL, init, 5 * 8, hipMemcpyHostToDevice, q));
-    if (++s->epoch == 0) s->epoch = 1;
-    HmsImportArgs a;
-    a.keys = keys;
-    a.counts = counts;
-    a.groups = groups;
-    a.hours = hours;
-    a.n = (uint64_t)n;
-    a.buckets = s->bk;
-    a.cb = s->cb;
-    a.zmin = s->zmin;
-    a.zmax = s->zmax;
-    a.base = s->base;
-    a.keys_out = s->lkeys + s->llen;
-    a.counts_out = s->lcounts + s->llen;
-    a.bflag = s->bflag;
-    a.epoch = s->epoch;
-    a.state = s->state;
-    hm_launch_stream_import(q, a);
-    const uint64_t nb = s->bk.mask + 1;
-    hm_launch_stream_collect(q, s->bflag, nb, s->epoch, s->blist, s->state);
-    HIPCHK(hipGetLastError());
-    /* the import's bucket list comes back with the state: a first part is
-     * copied unasked (an export of a time-ordered stream has few buckets), the
-     * rest only when there is more */
-    std::vector<uint32_t> list((size_t)std::min<uint64_t>({(uint64_t)n, nb, 1024}));
-    HIPCHK(hipMemcpyAsync(list.data(), s->blist, list.size() * 4, hipMemcpyDeviceToHost, q));
-    if ((st = stream_sync_state(s))) return st;
-    const unsigned long long e = s->hstate[HMS_ST_ERR];
-    if (e != ~0ull) {
-        ctx->last_err_index = (int64_t)(e >> 8);
-        ctx->last_err_kind = HM_E_ARG;
-        return HM_E_ARG;
-    }
-    if (s->hstate[HMS_ST_BFULL]) return HM_E_CAPACITY;   /* max_buckets (group, hour) pairs */
-    const uint64_t nlist = s->hstate[HMS_ST_NLIST];
-    if (nlist > nb) return HM_E_HIP;   /* cannot happen */
-    if (nlist > list.size()) {
-        list.resize((size_t)nlist);
-        HIPCHK(hipMemcpyAsync(list.data(), s->blist, (size_t)nlist * 4, hipMemcpyDeviceToHost, q));
-        HIPCHK(hm_sync(q));
-    }
-    /* compactness: the log's buckets stay exactly known (the import's list
-     * joins them); its keys stay distinct only when the caller promises the
-     * input's are and none of its buckets has cells in the log yet */
-    if (s->llen == 0) s->compact = true;
-    stream_appended(s, (uint64_t)n, list.data(), (uint32_t)nlist);
-    if (!(flags & HM_IMPORT_DISTINCT)) s->compact = false;
-    s->last_nparts = 1;   /* the next batch is counted speculatively as one bucket again */
-    return HM_OK;
-}
-
-extern "C" int hm_stream_extract(hm_stream* s, int64_t hour, uint64_t* keys_out, uint64_t* counts_out,
-                                 uint32_t* hours_out, int64_t capacity, int64_t* n_out)
-{
-    if (!s) return HM_E_ARG;
-    if (hour == HM_STREAM_ALLTIME)
-        return hm_stream_rollup(s, HM_SPAN_ALLTIME, 1, -1, keys_out, counts_out, nullptr, nullptr, capacity, n_out);
-    if (hour == HM_STREAM_EACH_HOUR)
-        return hm_stream_rollup(s, HM_SPAN_HOUR, 1, -1, keys_out, counts_out, nullptr, hours_out, capacity, n_out);
-    if (hour < (int64_t)s->base || hour - (int64_t)s->base >= HM_STREAM_MAX_HOURS) return HM_E_ARG;
-    return hm_stream_rollup(s, HM_SPAN_HOUR, 1, hour, keys_out, counts_out, nullptr, hours_out, capacity, n_out);
-}
-
-extern "C" int hm_stream_destroy(hm_stream* s)
-{
-    if (!s) return HM_OK;
-    premap_join(s);
-    if (s->ctx) (void)hipSetDevice(s->ctx->device);
-    if (s->ctx && s->ctx->stream) (void)hipStreamSynchronize(s->ctx->stream);
-    for (void* p : {(void*)s->state, (void*)s->bk.keys, (void*)s->bk_alt, (void*)s->bflag, (void*)s->blist,
-                    (void*)s->bloc, s->bids.p, s->rec.p, s->plat.p, s->plon.p, s->pkeep.p, s->pstart.p, s->pcnt.p,
-                    s->rk.p, s->rc.p, s->mk.p, s->mc.p})
-        if (p) (void)hipFree(p);
-    for (void* p : {(void*)s->lkeys, (void*)s->lcounts, (void*)s->akeys, (void*)s->acounts}) log_free(s, p);
-    if (s->hstate) (void)hipHostFree(s->hstate);
-    for (int t = 0; t < HMS_PAR; t++) {
-        for (void* p : {s->pk[t].p, s->pc[t].p})
-            if (p) (void)hipFree(p);
-        if (s->pctx[t]) {
-            hipStream_t q = s->pctx[t]->stream;
-            hm_ctx_destroy(s->pctx[t]);
-            if (q) (void)hipStreamDestroy(q);
-        }
-    }
-    if (s->pev) (void)hipEventDestroy(s->pev);
-    delete s;
     return HM_OK;
 }

@@ -306,11 +306,11 @@ class StreamingHeatmap:
         self._index = {"all": 0}
         # cells outside [0, 2^zmax)^2: (group, hour or UNDATED_HOUR, zoom, row, col, count)
         self._x = np.zeros((0, 6), dtype=np.int64)
+        self._query_n = {}             # cells of the last query of each kind (_query sizes the next from it)
         p = ctypes.c_void_p()
         rc = self.ctx.L.hm_stream_create(self.ctx.ptr, self.zmin, self.zmax, self.base_hour, int(initial_cells),
                                          int(max_buckets), ctypes.byref(p))
-        if rc != _lib.HM_OK:
-            _lib.raise_for(rc)
+        _lib.raise_for(rc)
         self.ptr = p
 
     # ------------------------------------------------------------------ input
@@ -388,9 +388,12 @@ class StreamingHeatmap:
         if rc == _lib.HM_E_EXOTIC:
             self._add_split(la, lo, kp, hr, gr, n)
             return
+        self._raise_point(rc)
+
+    def _raise_point(self, rc):
+        """raise_for with the index of the batch's first failing point"""
         if rc != _lib.HM_OK:
-            idx, kind = self.ctx.last_error()
-            _lib.raise_for(rc, idx)
+            _lib.raise_for(rc, self.ctx.last_error()[0])
 
     def _add_split(self, la, lo, kp, hr, gr, n):
         """The batch holds kept points outside the square: project once on the
@@ -403,9 +406,7 @@ class StreamingHeatmap:
         st = torch.empty(n, dtype=torch.uint8, device=la.device)
         rc = self.ctx.L.hm_project(self.ctx.ptr, device._ptr(la), device._ptr(lo), n, self.zmax, device._ptr(row),
                                    device._ptr(col), device._ptr(st))
-        if rc != _lib.HM_OK:      # before anything is inserted: the batch stays atomic
-            idx, kind = self.ctx.last_error()
-            _lib.raise_for(rc, idx)
+        self._raise_point(rc)     # before anything is inserted: the batch stays atomic
         lim = 1 << self.zmax
         out = (st == 0) & ((row < 0) | (row >= lim) | (col < 0) | (col >= lim))
         if kp is not None:
@@ -413,9 +414,7 @@ class StreamingHeatmap:
         keep_in = (~out).to(torch.uint8) if kp is None else (kp * (~out).to(torch.uint8))
         rc = self.ctx.L.hm_stream_add(self.ptr, device._ptr(la), device._ptr(lo), device._ptr(keep_in),
                                       device._ptr(hr), device._ptr(gr), n)
-        if rc != _lib.HM_OK:
-            idx, kind = self.ctx.last_error()
-            _lib.raise_for(rc, idx)
+        self._raise_point(rc)
         sel = out.nonzero().flatten()
         g = (gr[sel].to(torch.int64) & 0xFFFFFFFF) if gr is not None else torch.full_like(sel, NOGROUP)
         h = (hr[sel].to(torch.int64) & 0xFFFFFFFF) if hr is not None else torch.full_like(sel, UNDATED_HOUR)
@@ -434,8 +433,7 @@ class StreamingHeatmap:
         the log (one bucketed merge) when it holds repeated keys"""
         a, b = ctypes.c_int64(0), ctypes.c_int64(0)
         rc = self.ctx.L.hm_stream_cells(self.ptr, ctypes.byref(a), ctypes.byref(b), None)
-        if rc != _lib.HM_OK:
-            _lib.raise_for(rc)
+        _lib.raise_for(rc)
         return a.value, b.value
 
     def _log_capacity(self) -> int:
@@ -449,47 +447,61 @@ class StreamingHeatmap:
         self.ctx.L.hm_stream_cells(self.ptr, None, None, ctypes.byref(c))
         return c.value
 
+    def _query(self, call, extra: int, cap: int, memo_key=None):
+        """A capacity query: call(keys, counts, *extra int32 columns, cap,
+        n_out) -> status fills cap-sized CUDA tensors.  HM_E_CAPACITY with n >
+        cap: again at n + 1024.  n is remembered under memo_key (None: not) for
+        the caller's next starting capacity.  Returns (n, keys, counts,
+        *columns)."""
+        torch = self._torch
+        dev = "cuda:%d" % self.device_index
+        while True:
+            out = [torch.empty(cap, dtype=torch.int64 if j < 2 else torch.int32, device=dev) for j in range(2 + extra)]
+            n = ctypes.c_int64(0)
+            rc = call(*(device._ptr(t) for t in out), cap, ctypes.byref(n))
+            if rc == _lib.HM_E_CAPACITY and n.value > cap:
+                cap = n.value + 1024
+                continue
+            _lib.raise_for(rc)
+            if memo_key is not None:
+                self._query_n[memo_key] = n.value
+            return (n.value, *out)
+
+    @staticmethod
+    def _with_side(out, side):
+        """The host columns `out` with the matching columns `side` of the
+        out-of-square records (None: the stream holds none) appended."""
+        if side is None:
+            return out
+        return tuple(np.concatenate([a, np.asarray(b).astype(a.dtype)]) for a, b in zip(out, side))
+
+    @classmethod
+    def _host_cells(cls, n, keys, counts, columns=(), side=None):
+        """A query's first n device cells on the host: (*columns as uint32,
+        zoom, row, col, count), then the side records' columns (_with_side)."""
+        z, r, c = device.decode_keys(keys[:n].cpu().numpy().view(np.uint64))
+        out = (*(t[:n].cpu().numpy().view(np.uint32) for t in columns), z, r, c, counts[:n].cpu().numpy())
+        return cls._with_side(out, side)
+
     def rollup_device(self, timespan: str = "alltime", merge_groups: bool = True, select: int = -1):
         """(n, keys, counts, groups, periods) as torch CUDA tensors: the cells
         of `timespan` summed per (group, period), or over every group."""
-        torch = self._torch
         self.ctx.bind_stream()
         span = SPANS[timespan]
         # start from the last rollup of this kind (the log's capacity doubles as
         # batches arrive and can far exceed the distinct cells): a short
         # estimate costs one HM_E_CAPACITY retry with the exact size
-        memo = self.__dict__.setdefault("_rollup_n", {})
         mk = (span, bool(merge_groups), int(select))
-        cap = min(max(1024, self._log_capacity()), max(1024, int(memo.get(mk, 1 << 20) * 1.25) + 1024))
-        dev = "cuda:%d" % self.device_index
-        while True:
-            keys = torch.empty(cap, dtype=torch.int64, device=dev)
-            counts = torch.empty(cap, dtype=torch.int64, device=dev)
-            groups = torch.empty(cap, dtype=torch.int32, device=dev)
-            periods = torch.empty(cap, dtype=torch.int32, device=dev)
-            n = ctypes.c_int64(0)
-            rc = self.ctx.L.hm_stream_rollup(self.ptr, span, int(bool(merge_groups)), int(select), device._ptr(keys),
-                                             device._ptr(counts), device._ptr(groups), device._ptr(periods), cap,
-                                             ctypes.byref(n))
-            if rc == _lib.HM_E_CAPACITY and n.value > cap:
-                cap = n.value + 1024
-                continue
-            if rc != _lib.HM_OK:
-                _lib.raise_for(rc)
-            memo[mk] = n.value
-            return n.value, keys, counts, groups, periods
+        cap = min(max(1024, self._log_capacity()), max(1024, int(self._query_n.get(mk, 1 << 20) * 1.25) + 1024))
+        return self._query(lambda *out: self.ctx.L.hm_stream_rollup(self.ptr, span, int(bool(merge_groups)),
+                                                                    int(select), *out), 2, cap, mk)
 
     def rollup(self, timespan: str = "alltime", merge_groups: bool = True, select: int = -1):
         """Host arrays (group u32, period u32, zoom, row, col, count), cells
         outside the square included."""
         n, keys, counts, groups, periods = self.rollup_device(timespan, merge_groups, select)
-        z, r, c = device.decode_keys(keys[:n].cpu().numpy().view(np.uint64))
-        out = (groups[:n].cpu().numpy().view(np.uint32), periods[:n].cpu().numpy().view(np.uint32), z, r, c,
-               counts[:n].cpu().numpy())
-        if not len(self._x):
-            return out
-        x = self._exotic_rollup(timespan, merge_groups, select)
-        return tuple(np.concatenate([a, b.astype(a.dtype)]) for a, b in zip(out, x))
+        return self._host_cells(n, keys, counts, (groups, periods),
+                                self._exotic_rollup(timespan, merge_groups, select) if len(self._x) else None)
 
     def _exotic_rollup(self, timespan, merge_groups, select):
         """The out-of-square records summed per (group, period) of `timespan`
@@ -528,14 +540,9 @@ class StreamingHeatmap:
                 raise ValueError("pass hour or window, not both")
             return self.window_counts(*window)
         n, keys, counts, _ = self.extract_device(hour)
-        z, r, c = device.decode_keys(keys[:n].cpu().numpy().view(np.uint64))
-        cnt = counts[:n].cpu().numpy()
-        if len(self._x):
-            _, _, xz, xr, xc, xn = self._exotic_rollup("alltime" if hour == ALLTIME else "hour", True,
-                                                       -1 if hour == ALLTIME else int(hour))
-            z, r, c, cnt = (np.concatenate([z, xz.astype(z.dtype)]), np.concatenate([r, xr]),
-                            np.concatenate([c, xc]), np.concatenate([cnt, xn]))
-        return device.Counts(z, r, c, cnt, 0, [])
+        side = self._exotic_rollup("alltime" if hour == ALLTIME else "hour", True,
+                                   -1 if hour == ALLTIME else int(hour))[2:] if len(self._x) else None
+        return device.Counts(*self._host_cells(n, keys, counts, (), side), 0, [])
 
     # ------------------------------------------------- windows and retention
 
@@ -543,41 +550,22 @@ class StreamingHeatmap:
         """(n, keys, counts, groups) as torch CUDA tensors: the cells of the
         dated hours hour_lo <= hour < hour_hi summed per group, or over every
         group (hm_stream_window; out-of-square cells not included)."""
-        torch = self._torch
         self.ctx.bind_stream()
         if int(hour_hi) <= int(hour_lo):
             raise ValueError("a window needs hour_lo < hour_hi (got %d, %d)" % (hour_lo, hour_hi))
         # sized as rollup_device does: from the last window of this width
-        memo = self.__dict__.setdefault("_rollup_n", {})
         mk = ("window", bool(merge_groups), int(hour_hi) - int(hour_lo))
-        cap = min(max(1024, self._log_capacity()), max(1024, int(memo.get(mk, 1 << 20) * 1.25) + 1024))
-        dev = "cuda:%d" % self.device_index
-        while True:
-            keys = torch.empty(cap, dtype=torch.int64, device=dev)
-            counts = torch.empty(cap, dtype=torch.int64, device=dev)
-            groups = torch.empty(cap, dtype=torch.int32, device=dev)
-            n = ctypes.c_int64(0)
-            rc = self.ctx.L.hm_stream_window(self.ptr, int(hour_lo), int(hour_hi), int(bool(merge_groups)),
-                                             device._ptr(keys), device._ptr(counts), device._ptr(groups), cap,
-                                             ctypes.byref(n))
-            if rc == _lib.HM_E_CAPACITY and n.value > cap:
-                cap = n.value + 1024
-                continue
-            if rc != _lib.HM_OK:
-                _lib.raise_for(rc)
-            memo[mk] = n.value
-            return n.value, keys, counts, groups
+        cap = min(max(1024, self._log_capacity()), max(1024, int(self._query_n.get(mk, 1 << 20) * 1.25) + 1024))
+        return self._query(lambda *out: self.ctx.L.hm_stream_window(self.ptr, int(hour_lo), int(hour_hi),
+                                                                    int(bool(merge_groups)), *out), 1, cap, mk)
 
     def window(self, hour_lo: int, hour_hi: int, merge_groups: bool = True):
         """Host arrays (group u32, zoom, row, col, count) of the window, cells
         outside the square included."""
         n, keys, counts, groups = self.window_device(hour_lo, hour_hi, merge_groups)
-        z, r, c = device.decode_keys(keys[:n].cpu().numpy().view(np.uint64))
-        out = (groups[:n].cpu().numpy().view(np.uint32), z, r, c, counts[:n].cpu().numpy())
-        if not len(self._x):
-            return out
-        x = _window_records(self._x, int(hour_lo), int(hour_hi), merge_groups)
-        return tuple(np.concatenate([a, x[:, j].astype(a.dtype)]) for j, a in enumerate(out))
+        return self._host_cells(n, keys, counts, (groups,),
+                                _window_records(self._x, int(hour_lo), int(hour_hi), merge_groups).T
+                                if len(self._x) else None)
 
     def window_counts(self, hour_lo: int, hour_hi: int) -> device.Counts:
         """Cells of every kept point of the hours hour_lo <= hour < hour_hi."""
@@ -622,7 +610,6 @@ class StreamingHeatmap:
         undated ones included) or (lo, hi), summed over every group
         ('merged'), per group ('each') or of one group id (hm_stream_view;
         out-of-square cells not included)."""
-        torch = self._torch
         self.ctx.bind_stream()
         rects, lo, hi, gw = self._view_args(rects, hours, group)
         ra = (ctypes.c_int64 * (5 * len(rects)))(*[v for r in rects for v in r])
@@ -631,40 +618,23 @@ class StreamingHeatmap:
         # HM_E_CAPACITY retry with the exact size when that is short)
         area = sum((min(rhi, 1 << z) - max(rlo, 0)) * (min(chi, 1 << z) - max(clo, 0))
                    for z, rlo, rhi, clo, chi in rects if min(rhi, chi) > 0 and max(rlo, clo) < (1 << z))
-        memo = self.__dict__.setdefault("_rollup_n", {})
         mk = ("view", tuple(rects), gw if gw < 0 else 0)
         if gw == _lib.HM_VIEW_EACH:
-            cap = max(1024, int(memo.get(mk, min(area, 1 << 20)) * 1.25) + 1024)
+            cap = max(1024, int(self._query_n.get(mk, min(area, 1 << 20)) * 1.25) + 1024)
         else:
-            cap = max(1024, min(area, int(memo.get(mk, 1 << 20) * 1.25) + 1024))
+            cap = max(1024, min(area, int(self._query_n.get(mk, 1 << 20) * 1.25) + 1024))
         cap = min(max(1024, self._log_capacity()), cap)
-        dev = "cuda:%d" % self.device_index
-        while True:
-            keys = torch.empty(cap, dtype=torch.int64, device=dev)
-            counts = torch.empty(cap, dtype=torch.int64, device=dev)
-            groups = torch.empty(cap, dtype=torch.int32, device=dev)
-            n = ctypes.c_int64(0)
-            rc = self.ctx.L.hm_stream_view(self.ptr, lo, hi, gw, ra, len(rects), device._ptr(keys),
-                                           device._ptr(counts), device._ptr(groups), cap, ctypes.byref(n))
-            if rc == _lib.HM_E_CAPACITY and n.value > cap:
-                cap = n.value + 1024
-                continue
-            if rc != _lib.HM_OK:
-                _lib.raise_for(rc)
-            memo[mk] = n.value
-            return n.value, keys, counts, groups
+        return self._query(lambda *out: self.ctx.L.hm_stream_view(self.ptr, lo, hi, gw, ra, len(rects), *out), 1, cap,
+                           mk)
 
     def view(self, rects, hours=None, group="merged"):
         """Host arrays (group u32, zoom, row, col, count) of the view, with
         the out-of-square cells that lie in the rectangles as given (not
         clipped)."""
         n, keys, counts, groups = self.view_device(rects, hours, group)
-        z, r, c = device.decode_keys(keys[:n].cpu().numpy().view(np.uint64))
-        out = (groups[:n].cpu().numpy().view(np.uint32), z, r, c, counts[:n].cpu().numpy())
-        if not len(self._x):
-            return out
-        x = _view_records(self._x, [tuple(int(v) for v in q) for q in rects], hours, group)
-        return tuple(np.concatenate([a, x[:, j].astype(a.dtype)]) for j, a in enumerate(out))
+        return self._host_cells(n, keys, counts, (groups,),
+                                _view_records(self._x, [tuple(int(v) for v in q) for q in rects], hours, group).T
+                                if len(self._x) else None)
 
     def view_counts(self, rects, hours=None) -> device.Counts:
         """Cells of every kept point inside the rectangles (and the hours)."""
@@ -754,8 +724,7 @@ class StreamingHeatmap:
             part = tiles[j:j + _lib.HM_RASTER_MAX_TILES]
             rc = self.ctx.L.hm_stream_raster(self.ptr, lo, hi, gw, _raster._tile_array(part), len(part), b, h,
                                              device._ptr(grid[j:j + len(part)]))
-            if rc != _lib.HM_OK:
-                _lib.raise_for(rc)
+            _lib.raise_for(rc)
         return grid
 
     def tile_images(self, tiles, hours=None, user=None, bins_log2=8, radius=2, scale="log", vmax=None, ramp="heat"):
@@ -775,8 +744,7 @@ class StreamingHeatmap:
         self.ctx.bind_stream()
         a, b = ctypes.c_int64(0), ctypes.c_int64(0)
         rc = self.ctx.L.hm_stream_expire(self.ptr, int(before_hour), ctypes.byref(a), ctypes.byref(b))
-        if rc != _lib.HM_OK:
-            _lib.raise_for(rc)
+        _lib.raise_for(rc)
         self._x, gone = _expire_records(self._x, int(before_hour))
         return a.value + gone, b.value
 
@@ -788,37 +756,19 @@ class StreamingHeatmap:
         (hm_stream_export: hm_count key layout, group NOGROUP for none, hour
         HM_STREAM_UNDATED's bits for an undated cell; out-of-square cells not
         included)."""
-        torch = self._torch
         self.ctx.bind_stream()
         cap = max(1, self.cells()[0])      # exact: the export compacts the log as cells() does
-        dev = "cuda:%d" % self.device_index
-        while True:
-            keys = torch.empty(cap, dtype=torch.int64, device=dev)
-            counts = torch.empty(cap, dtype=torch.int64, device=dev)
-            groups = torch.empty(cap, dtype=torch.int32, device=dev)
-            hours = torch.empty(cap, dtype=torch.int32, device=dev)
-            n = ctypes.c_int64(0)
-            rc = self.ctx.L.hm_stream_export(self.ptr, device._ptr(keys), device._ptr(counts), device._ptr(groups),
-                                             device._ptr(hours), cap, ctypes.byref(n))
-            if rc == _lib.HM_E_CAPACITY and n.value > cap:
-                cap = n.value + 1024
-                continue
-            if rc != _lib.HM_OK:
-                _lib.raise_for(rc)
-            return n.value, keys, counts, groups, hours
+        return self._query(lambda *out: self.ctx.L.hm_stream_export(self.ptr, *out), 2, cap)
 
     def export(self):
         """Host arrays (group u32, hour int64, zoom, row, col, count) of every
         record held, hour UNDATED_HOUR (-1) for undated cells, cells outside
         the square included."""
         n, keys, counts, groups, hours = self.export_device()
-        z, r, c = device.decode_keys(keys[:n].cpu().numpy().view(np.uint64))
-        h = hours[:n].cpu().numpy().view(np.uint32).astype(np.int64)
+        g, h, z, r, c, cnt = self._host_cells(n, keys, counts, (groups, hours))
+        h = h.astype(np.int64)
         h[h == _lib.HM_STREAM_UNDATED] = UNDATED_HOUR
-        out = (groups[:n].cpu().numpy().view(np.uint32), h, z, r, c, counts[:n].cpu().numpy())
-        if not len(self._x):
-            return out
-        return tuple(np.concatenate([a, self._x[:, j].astype(a.dtype)]) for j, a in enumerate(out))
+        return self._with_side((g, h, z, r, c, cnt), self._x.T if len(self._x) else None)
 
     def _cells_u32(self, x, n, what, undated=False):
         """uint32 values per cell as an int32 device tensor (their bits).
@@ -897,8 +847,7 @@ class StreamingHeatmap:
             raise ValueError("cell %d is not a valid cell of this stream (zooms %d..%d, row and col inside the "
                              "square, count >= 1, group <= 0x%X, hour undated or in [%d, %d))"
                              % (idx, self.zmin, self.zmax, NOGROUP, self.base_hour, self.base_hour + MAX_HOURS))
-        if rc != _lib.HM_OK:
-            _lib.raise_for(rc)
+        _lib.raise_for(rc)
         self._index, self.labels, self._explicit_max = index, new_labels, explicit_max
 
     def snapshot(self) -> dict:
