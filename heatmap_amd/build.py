@@ -18,10 +18,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "_lib")
 LIB = os.path.join(LIBDIR, "libheatmap_amd.so")
-SOURCES = ["hm_kernels.hip", "hm_general.hip", "hm_stream.hip", "hm_merge.hip", "hm_raster.hip", "hm_api.cpp",
-           "hm_stream_api.cpp", "hm_host.c"]
-HEADERS = ["hm_common.h", "hm_device.h", "hm_glibc_emul.h", "hm_branred.h", "hm_project.h", "hm_pipeline.h",
-           "hm_ytab.h", "hm_table.h", "hm_ctx.h", "hm_stream_rect.h"]
+SOURCES = ["hm_kernels.hip", "hm_aggregate.hip", "hm_general.hip", "hm_stream.hip", "hm_merge.hip", "hm_raster.hip",
+           "hm_api.cpp", "hm_stream_api.cpp", "hm_host.c"]
 ARCH = os.environ.get("HM_OFFLOAD_ARCH", "gfx950")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "--offload-arch=" + ARCH,
          "-Wall", "-Wno-unused-function", "-Wno-unused-variable", "-Wno-unknown-pragmas",
@@ -37,7 +35,8 @@ def _stale() -> bool:
     if os.path.getmtime(os.path.join(CSRC, SCALAR_SRC)) > os.path.getmtime(scalar_module_path()):
         return True
     t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, f) for f in SOURCES + HEADERS]
+    # every source and header in csrc/: no list of headers to keep by hand
+    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".hip", ".cpp", ".c"))]
     deps.append(os.path.join(os.path.dirname(HERE), "include", "heatmap_amd.h"))
     return any(os.path.getmtime(d) > t for d in deps)
 
@@ -52,7 +51,10 @@ def build(force: bool = False, verbose: bool = True, out: str = None, defines=()
     os.makedirs(os.path.dirname(lib), exist_ok=True)
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     objs, procs = [], []
-    for src in SOURCES:   # the translation units compile in parallel
+    sources = SOURCES
+    if csrc:   # another tree (a commit's sources for an A/B): whatever translation units it holds
+        sources = sorted(f for f in os.listdir(csrc) if f.endswith((".hip", ".cpp", ".c")) and f != SCALAR_SRC)
+    for src in sources:   # the translation units compile in parallel
         obj = os.path.join(os.path.dirname(lib), os.path.basename(lib) + "." + src.rsplit(".", 1)[0] + ".o")
         if src.endswith(".c"):   # host C (hm_project_scalar): gcc, contraction off as everywhere
             cmd = [os.environ.get("CC", "gcc"), *HOST_FLAGS, "-c", os.path.join(src_dir, src), "-o", obj]

@@ -1,7 +1,7 @@
 /* gfx950 kernels of the general count path.
  *
- * The fast pipeline (hm_kernels.hip) counts the points of one group whose
- * zoom-Z tile lies in [0, 2^Z)^2.  Everything else is counted here:
+ * The fast pipeline (hm_kernels.hip, hm_aggregate.hip) counts the points of one
+ * group whose zoom-Z tile lies in [0, 2^Z)^2.  Everything else is counted here:
  *   - kept points whose tile lies outside that square: |lat| > 85.0511...,
  *     lon outside [-180, 180).  The reference bins them with negative rows and
  *     columns >= 2^z (tile.py:17,21 has no clamp; heatmap.py:27-36 keeps them);
@@ -68,62 +68,6 @@ __device__ __forceinline__ hm_u128 hm_kshfl_down(hm_u128 k)
 {
     return ((hm_u128)__shfl_down((unsigned long long)(k >> 64), 1, 64) << 64) |
            (hm_u128)__shfl_down((unsigned long long)k, 1, 64);
-}
-
-/* OR / AND of the keys into orand[0..3] (lo, hi | lo, hi) */
-__device__ __forceinline__ void hm_orand_flush(unsigned long long* orand, unsigned long long o_lo,
-                                               unsigned long long o_hi, unsigned long long n_lo,
-                                               unsigned long long n_hi)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        o_lo |= __shfl_xor(o_lo, o, 64);
-        o_hi |= __shfl_xor(o_hi, o, 64);
-        n_lo &= __shfl_xor(n_lo, o, 64);
-        n_hi &= __shfl_xor(n_hi, o, 64);
-    }
-    if (hm_lane() == 0) {
-        atomicOr(&orand[0], o_lo);
-        atomicOr(&orand[1], o_hi);
-        atomicAnd(&orand[2], n_lo);
-        atomicAnd(&orand[3], n_hi);
-    }
-}
-
-/* the same, one set of atomics per 256-thread block (every thread calls):
- * same-address atomics serialise (~88 per us a word) */
-__device__ __forceinline__ void hm_orand_flush_block(unsigned long long* orand, unsigned long long o_lo,
-                                                     unsigned long long o_hi, unsigned long long n_lo,
-                                                     unsigned long long n_hi)
-{
-    __shared__ unsigned long long red[4][4];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        o_lo |= __shfl_xor(o_lo, o, 64);
-        o_hi |= __shfl_xor(o_hi, o, 64);
-        n_lo &= __shfl_xor(n_lo, o, 64);
-        n_hi &= __shfl_xor(n_hi, o, 64);
-    }
-    const int w = threadIdx.x >> 6;
-    if (hm_lane() == 0) {
-        red[0][w] = o_lo;
-        red[1][w] = o_hi;
-        red[2][w] = n_lo;
-        red[3][w] = n_hi;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int q = 1; q < 4; q++) {
-            o_lo |= red[0][q];
-            o_hi |= red[1][q];
-            n_lo &= red[2][q];
-            n_hi &= red[3][q];
-        }
-        atomicOr(&orand[0], o_lo);
-        atomicOr(&orand[1], o_hi);
-        atomicAnd(&orand[2], n_lo);
-        atomicAnd(&orand[3], n_hi);
-    }
 }
 
 __global__ __launch_bounds__(256) void k_gen_keys(HmGenArgs a)
@@ -909,8 +853,8 @@ __global__ __launch_bounds__(HM_OS_THREADS) void k_rx_onesweep(HmRxPass a)
 }
 
 /* grouped counts from tiles (hm_count_grouped_tiles): list the kept ones,
- * one output reservation per block step of 256 * HM_TL_PPT points (as
- * k_project_list: a per-wave reservation on one counter saturates it) */
+ * one output reservation per block step of 256 * HM_TL_PPT points
+ * (hm_block_reserve: a per-wave reservation on one counter saturates it) */
 #define HM_TL_PPT 16
 __global__ __launch_bounds__(256) void k_tiles_list(const int64_t* __restrict__ rows, const int64_t* __restrict__ cols,
                                                     const uint8_t* __restrict__ keep, const uint32_t* __restrict__ group,
@@ -929,10 +873,7 @@ __global__ __launch_bounds__(256) void k_tiles_list(const int64_t* __restrict__ 
         }
         uint32_t tot;
         uint32_t pos = hm_block_excl_scan<256>((uint32_t)__popc(pm), scr, &tot);
-        if (threadIdx.x == 0) base_s = tot ? atomicAdd(count, (unsigned long long)tot) : 0ull;
-        __syncthreads();
-        const unsigned long long b = base_s;
-        __syncthreads();
+        const unsigned long long b = hm_block_reserve(count, tot, &base_s);
 #pragma unroll
         for (int k = 0; k < HM_TL_PPT; k++) {
             if ((pm >> k) & 1u) {
@@ -951,16 +892,9 @@ __global__ __launch_bounds__(256) void k_tiles_list(const int64_t* __restrict__ 
 /* launchers                                                                 */
 /* ------------------------------------------------------------------------ */
 
-static unsigned hm_ggrid(uint64_t n, unsigned per, unsigned cap)
-{
-    uint64_t b = (n + per - 1) / per;
-    if (b > cap) b = cap;
-    return (unsigned)(b ? b : 1);
-}
-
 void hm_launch_gen_keys(hipStream_t s, const HmGenArgs& a)
 {
-    hipLaunchKernelGGL(k_gen_keys, dim3(hm_ggrid(a.n, 256, 4096)), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_gen_keys, dim3(hm_grid(a.n, 256, 4096)), dim3(256), 0, s, a);
 }
 
 uint64_t hm_rx_os_tiles(uint64_t n) { return (n + HM_OS_TILE_MIN - 1) / HM_OS_TILE_MIN; }
@@ -984,9 +918,9 @@ int hm_launch_rx_sort(hipStream_t s, bool wide, uint64_t* const* lo, uint64_t* c
     for (int p = 0; p < np; p++) h.sh[p] = sh[p];
     h.hist = (unsigned long long*)(state + 256);
     if (wide)
-        hipLaunchKernelGGL(k_rx_hist_all<hm_u128>, dim3(hm_ggrid(n, 256 * 16, 2048)), dim3(256), 0, s, h);
+        hipLaunchKernelGGL(k_rx_hist_all<hm_u128>, dim3(hm_grid(n, 256 * 16, 2048)), dim3(256), 0, s, h);
     else
-        hipLaunchKernelGGL(k_rx_hist_all<uint64_t>, dim3(hm_ggrid(n, 256 * 16, 2048)), dim3(256), 0, s, h);
+        hipLaunchKernelGGL(k_rx_hist_all<uint64_t>, dim3(hm_grid(n, 256 * 16, 2048)), dim3(256), 0, s, h);
     hipLaunchKernelGGL(k_rx_digit_offsets, dim3(np), dim3(64), 0, s, h.hist);
     int cur = 0;
     for (int p = 0; p < np; p++) {
@@ -1002,9 +936,9 @@ int hm_launch_rx_sort(hipStream_t s, bool wide, uint64_t* const* lo, uint64_t* c
         x.epoch = (uint64_t)p + 1;
         x.ticket = (unsigned*)state + p;
         if (wide)
-            hipLaunchKernelGGL(k_rx_onesweep<hm_u128>, dim3(hm_ggrid(nt, 1, 512)), dim3(HM_OS_THREADS), 0, s, x);
+            hipLaunchKernelGGL(k_rx_onesweep<hm_u128>, dim3(hm_grid(nt, 1, 512)), dim3(HM_OS_THREADS), 0, s, x);
         else
-            hipLaunchKernelGGL(k_rx_onesweep<uint64_t>, dim3(hm_ggrid(nt, 1, 1024)), dim3(HM_OS_THREADS), 0, s, x);
+            hipLaunchKernelGGL(k_rx_onesweep<uint64_t>, dim3(hm_grid(nt, 1, 1024)), dim3(HM_OS_THREADS), 0, s, x);
         cur = 1 - cur;
     }
     return cur;
@@ -1014,24 +948,24 @@ void hm_launch_cascade(hipStream_t s, const HmCascArgs& a, uint64_t bound, int e
 {
     if (emit_only == 2) {   /* two zoom steps (k_cascade2) */
         if (wide)
-            hipLaunchKernelGGL(k_cascade2<hm_u128>, dim3(hm_ggrid(bound, HM_CS2_TILE, 2048)), dim3(HM_CS_THREADS), 0,
+            hipLaunchKernelGGL(k_cascade2<hm_u128>, dim3(hm_grid(bound, HM_CS2_TILE, 2048)), dim3(HM_CS_THREADS), 0,
                                s, a);
         else
-            hipLaunchKernelGGL(k_cascade2<uint64_t>, dim3(hm_ggrid(bound, HM_CS2_TILE, 2048)), dim3(HM_CS_THREADS), 0,
+            hipLaunchKernelGGL(k_cascade2<uint64_t>, dim3(hm_grid(bound, HM_CS2_TILE, 2048)), dim3(HM_CS_THREADS), 0,
                                s, a);
         return;
     }
     if (emit_only) {
         if (wide)
-            hipLaunchKernelGGL(k_cascade_emit<hm_u128>, dim3(hm_ggrid(bound, 256, 4096)), dim3(256), 0, s, a);
+            hipLaunchKernelGGL(k_cascade_emit<hm_u128>, dim3(hm_grid(bound, 256, 4096)), dim3(256), 0, s, a);
         else
-            hipLaunchKernelGGL(k_cascade_emit<uint64_t>, dim3(hm_ggrid(bound, 256, 4096)), dim3(256), 0, s, a);
+            hipLaunchKernelGGL(k_cascade_emit<uint64_t>, dim3(hm_grid(bound, 256, 4096)), dim3(256), 0, s, a);
     } else {
         if (wide)
-            hipLaunchKernelGGL(k_cascade<hm_u128>, dim3(hm_ggrid(bound, HM_CS_TILE, 2048)), dim3(HM_CS_THREADS), 0, s,
+            hipLaunchKernelGGL(k_cascade<hm_u128>, dim3(hm_grid(bound, HM_CS_TILE, 2048)), dim3(HM_CS_THREADS), 0, s,
                                a);
         else
-            hipLaunchKernelGGL(k_cascade<uint64_t>, dim3(hm_ggrid(bound, HM_CS_TILE, 2048)), dim3(HM_CS_THREADS), 0,
+            hipLaunchKernelGGL(k_cascade<uint64_t>, dim3(hm_grid(bound, HM_CS_TILE, 2048)), dim3(HM_CS_THREADS), 0,
                                s, a);
     }
 }
@@ -1047,7 +981,7 @@ void hm_launch_tiles_list(hipStream_t s, const int64_t* rows, const int64_t* col
                           const uint32_t* group, int64_t n, int64_t* row, int64_t* col, uint32_t* grp, int64_t* idx,
                           unsigned long long* count)
 {
-    hipLaunchKernelGGL(k_tiles_list, dim3(hm_ggrid((uint64_t)n, 256 * HM_TL_PPT, 4096)), dim3(256), 0, s, rows, cols, keep, group,
+    hipLaunchKernelGGL(k_tiles_list, dim3(hm_grid((uint64_t)n, 256 * HM_TL_PPT, 4096)), dim3(256), 0, s, rows, cols, keep, group,
                        n, row, col, grp, idx, count);
 }
 

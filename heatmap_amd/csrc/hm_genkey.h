@@ -1,5 +1,5 @@
 /* 128-bit cell keys of the general path (hm_general.hip), shared with the
- * list kernels that build them while projecting (hm_kernels.hip):
+ * kernels that build them while projecting (hm_kernels.hip):
  *     sr + 16 (5) | sc + 2^47 (48) | group (32) | morton(ro, co) (2Z)
  * sr = row >> Z, sc = col >> Z (arithmetic) name the zoom-0 "super tile";
  * ro, co are the tile's offsets inside it.  The group sits right above the
@@ -9,6 +9,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "hm_device.h"
 
 typedef unsigned __int128 hm_u128;
 
@@ -61,4 +62,52 @@ __device__ __forceinline__ void hm_gen_decode(hm_u128 k, int Z, int z, uint32_t*
     /* sr * 2^z, sc * 2^z as unsigned shifts (two's complement) */
     *row = (int64_t)(((uint64_t)sr << z) + hm_compact21(m >> 1));
     *col = (int64_t)(((uint64_t)sc << z) + hm_compact21(m));
+}
+
+/* OR / AND of the keys into orand[0..3] (lo, hi | lo, hi): the radix sort
+ * skips the digits every key agrees on.  Same-address atomics serialise (~88
+ * per us a word), so the flush is per block; k_project_keys_slow
+ * (hm_kernels.hip) has a per-wave form of its own. */
+
+/* the wave's reduction, in every lane */
+__device__ __forceinline__ void hm_orand_wave(unsigned long long& o_lo, unsigned long long& o_hi,
+                                              unsigned long long& n_lo, unsigned long long& n_hi)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        o_lo |= __shfl_xor(o_lo, o, 64);
+        o_hi |= __shfl_xor(o_hi, o, 64);
+        n_lo &= __shfl_xor(n_lo, o, 64);
+        n_hi &= __shfl_xor(n_hi, o, 64);
+    }
+}
+
+/* one set of atomics per 256-thread block (every thread calls): per wave they
+ * were 32K same-address atomics a word for 1e8 points */
+__device__ __forceinline__ void hm_orand_flush_block(unsigned long long* orand, unsigned long long o_lo,
+                                                     unsigned long long o_hi, unsigned long long n_lo,
+                                                     unsigned long long n_hi)
+{
+    __shared__ unsigned long long red[4][4];
+    hm_orand_wave(o_lo, o_hi, n_lo, n_hi);
+    const int w = threadIdx.x >> 6;
+    if (hm_lane() == 0) {
+        red[0][w] = o_lo;
+        red[1][w] = o_hi;
+        red[2][w] = n_lo;
+        red[3][w] = n_hi;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int q = 1; q < 4; q++) {
+            o_lo |= red[0][q];
+            o_hi |= red[1][q];
+            n_lo &= red[2][q];
+            n_hi &= red[3][q];
+        }
+        atomicOr(&orand[0], o_lo);
+        atomicOr(&orand[1], o_hi);
+        atomicAnd(&orand[2], n_lo);
+        atomicAnd(&orand[3], n_hi);
+    }
 }

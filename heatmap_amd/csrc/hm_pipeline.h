@@ -1,4 +1,47 @@
-/* Shared host/device declarations of the count pipeline (see hm_kernels.hip). */
+/* Shared host/device declarations of the count pipeline.
+ *
+ * Path (SURVEY.md section 8a, a-1 .. a-11), one hm_count() call:
+ *
+ *   k_project_partition   fp64 lat/lon SoA -> tile row/col at zoom Z (exact,
+ *                         hm_project.h) -> row-major key -> LDS counting sort of an
+ *                         8192-point tile by the key's top digit (zoom z1
+ *                         tile); writes the tile's keys (u32/u16, top digit
+ *                         dropped) contiguously and one run record per
+ *                         non-empty digit.  Reads 16 B/point, writes 4 B/point.
+ *   k_partition           the same counting sort one level down, gathering a
+ *                         parent bucket's runs (wave per run).  Levels stop at
+ *                         zoom zb = Z - 7, whose buckets hold 128x128 zoom-Z
+ *                         bins.
+ *   k_aggregate           per zoom-zb bucket: LDS-privatised dense 128x128 u32
+ *                         histogram of the u16 in-bucket keys (wave-aggregated
+ *                         atomics), then an in-LDS 4:1 pyramid emitting every
+ *                         non-empty cell of zooms Z .. zb+1.  Buckets larger
+ *                         than one work item merge through global atomics and
+ *                         k_aggregate_merged emits them.
+ *   k_pool                per parent bucket: dense LDS array of its children's
+ *                         totals -> 4:1 pyramid -> zooms z_l .. z_{l-1}+1; the
+ *                         root emits zooms z1 .. 0.
+ *   k_runscan / scans / k_compact: turn per-digit run counters into compact,
+ *                         parent-major bucket lists and work-item prefixes.
+ *
+ * Every coarser tile is a right shift of the zoom-Z row and column, which is
+ * the reference's tile-centre re-projection on the shift window (SURVEY.md
+ * a-4) and the direct projection at every zoom (a-1).  Counts are integers (u32
+ * per call, u64 out): the reference's float sums of 1.0 are exact below 2^53.
+ *
+ * The kernels:
+ *   hm_kernels.hip    level 1 (k_project_partition, k_l1_fast and the kernels
+ *                     around them), the levels >= 2 (k_partition,
+ *                     k_partition_fr, run scan, hot runs, scans, k_compact),
+ *                     k_project, the general path's keys from lat/lon,
+ *                     k_fill, k_synth, k_read_stream
+ *   hm_aggregate.hip  emission and pyramids, k_aggregate, the small-bucket
+ *                     kernels, k_pool
+ *   hm_runs.h         work items and run streaming, shared by those two
+ *   hm_general.hip    the general count path: keys from tiles, radix sort,
+ *                     zoom cascade
+ *   hm_stamps.h       phase stamps of the profiling builds
+ */
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -163,6 +206,14 @@ inline dim3 hm_grid2(uint32_t nblocks)
 {
     const uint32_t x = nblocks < 65536u ? (nblocks ? nblocks : 1u) : 65536u;
     return dim3(x, (nblocks + x - 1) / x);
+}
+
+/* blocks of a grid-stride launch: ceil(n / per), clamped to [1, cap] */
+inline unsigned hm_grid(uint64_t n, unsigned per, unsigned cap)
+{
+    uint64_t b = (n + per - 1) / per;
+    if (b > cap) b = cap;
+    return (unsigned)(b ? b : 1);
 }
 
 /* Flat run list of a level: run j holds cnt = run[j].y keys starting at key
@@ -491,10 +542,6 @@ void hm_launch_redo(hipStream_t s, const HmRedoArgs& a, uint64_t n);
  * ones: the exotic list outgrew its first capacity.  rows/cols: tile input */
 void hm_launch_collect_exotic(hipStream_t s, const double* lat, const double* lon, const int64_t* rows,
                               const int64_t* cols, const uint8_t* keep, int64_t n, int Z, HmExotic x);
-/* grouped counts: project every point exactly (errors), list the kept ones */
-void hm_launch_project_list(hipStream_t s, const double* lat, const double* lon, const uint8_t* keep,
-                            const uint32_t* group, int64_t n, int Z, int64_t* row, int64_t* col, uint32_t* grp,
-                            int64_t* idx, unsigned long long* count, unsigned long long* err_word);
 /* few_runs: every parent item spans <= HM_L1_SHARDS runs (parents are the
  * level-1 regions): k_partition_fr, else k_partition */
 void hm_launch_partN(hipStream_t s, const HmPartNArgs& a, uint32_t items, bool out16, bool few_runs);

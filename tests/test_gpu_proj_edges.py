@@ -4,7 +4,7 @@
 Five kernels carry a copy of the accept-or-defer decision that bit-exact
 tiles depend on: k_l1_fast (hm_project_l1), k_project_partition and
 k_project_keys_fast (hm_project_fast), k_project / k_redo / k_collect_exotic /
-k_project_list / k_project_keys / k_project_keys_slow (hm_project_point or the
+k_project_keys_slow (hm_project_point or the
 exact chain).  test_proj_edges_host.py shows that the statements, compiled for
 the host, agree with the oracle on the catalogue; here the device executes
 them, and the plumbing around them -- redo list, tile re-feed, exotic list,
@@ -320,7 +320,7 @@ def test_redo_overflow(gpu, host_math, kind, keep):
 
 
 # --------------------------------------------------------------------------
-# the general path of hm_count: k_project_list / k_project_keys
+# the general path of hm_count: k_project_keys_fast / k_project_keys_slow
 # --------------------------------------------------------------------------
 
 GEN_Z = 21

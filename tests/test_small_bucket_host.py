@@ -1,5 +1,5 @@
 """CPU: the counting identities the small-bucket kernels rely on
-(heatmap_amd/csrc/hm_kernels.hip, hm_small_sort / hm_small_emit), restated
+(heatmap_amd/csrc/hm_aggregate.hip, hm_small_sort / hm_small_emit), restated
 in numpy and checked against a direct count of distinct cells per level.
 
 A bucket's keys are 2*lg-bit Morton codes (col bits even, row bits odd); the

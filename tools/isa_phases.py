@@ -3,10 +3,11 @@
 
     python tools/isa_phases.py [--mode 4] [--kernel 'k_l1_fast<uint32_t,false>'] [-D NAME=V ...] [--csrc DIR]
 
-Compiles hm_kernels.hip to assembly with the build's own flags plus
--DHM_ISA_MARKS=<mode>, which turns the HM_STAMP_M(<mode>, n) sites of that
-kernel (the phase-stamp sites of tools/stamps.py) into assembly comments, and
-prints for the text between consecutive marks the number of VALU, SALU, LDS,
+Compiles the source that holds the kernel (MODE_FILES: hm_kernels.hip for
+modes 1 to 4, hm_aggregate.hip for 5 and 7) to assembly with the build's own
+flags plus -DHM_ISA_MARKS=<mode>, which turns the HM_STAMP_M(<mode>, n) sites
+of that kernel (the phase-stamp sites of tools/stamps.py) into assembly
+comments, and prints for the text between consecutive marks the number of VALU, SALU, LDS,
 VMEM, SMEM, s_waitcnt and branch instructions (classified by mnemonic prefix
 only), then the kernel's VGPRs, SGPRs, scratch and spills.  Three counts per
 phase follow serial chains: the vmcnt waits before the phase's last VMEM
@@ -30,6 +31,9 @@ MODE_NAMES = {
     2: ["issue+lds_setup", "project(loads)", "redo+count_rank", "reserve+scan", "stage", "dbase", "copy"],
     4: ["issue+lds_setup", "project(loads)", "redo+count_rank", "reserve+scan", "stage", "copy"],
 }
+# the source file that holds the kernel of each stamp mode (csrc/hm_stamps.h)
+MODE_FILES = {1: "hm_kernels.hip", 2: "hm_kernels.hip", 3: "hm_kernels.hip", 4: "hm_kernels.hip",
+              5: "hm_aggregate.hip", 7: "hm_aggregate.hip"}
 CLASSES = ["VALU", "SALU", "LDS", "VMEM", "SMEM", "waitcnt", "branch"]
 VMEM_PREFIXES = ("global_", "buffer_", "flat_", "scratch_")
 BRANCH_PREFIXES = ("s_cbranch", "s_branch", "s_setpc", "s_swappc", "s_call")
@@ -53,13 +57,16 @@ def classify(mn):
     return None
 
 
-def compile_asm(csrc, mode, defines, keep=None):
+def compile_asm(csrc, mode, defines, keep=None, source=None):
+    """Device assembly of `source` (default: the file of `mode`'s kernel);
+    mode None: no marks, the code as the build compiles it."""
     from heatmap_amd import build as b
 
     out = tempfile.NamedTemporaryFile(suffix=".s", delete=False).name
     flags = [f for f in b.FLAGS if f != "-fPIC"]
-    cmd = [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), *flags, "-DHM_ISA_MARKS=%d" % mode,
-           *["-D" + d for d in defines], "-S", "--cuda-device-only", os.path.join(csrc, "hm_kernels.hip"), "-o", out]
+    marks = [] if mode is None else ["-DHM_ISA_MARKS=%d" % mode]
+    cmd = [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), *flags, *marks, *["-D" + d for d in defines], "-S",
+           "--cuda-device-only", os.path.join(csrc, source or MODE_FILES[mode]), "-o", out]
     subprocess.check_call(cmd)
     text = open(out).read()
     if keep:

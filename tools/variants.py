@@ -95,7 +95,7 @@ VARIANTS = {
 PATCH_DEFINES = {}
 PATCHES = {
     # k_partition / k_aggregate run bodies: no global key loads
-    "noload": [("hm_kernels.hip", "                        x[u] = kv[L.bv[r] + (v - L.pre[r])];",
+    "noload": [("hm_runs.h", "                        x[u] = kv[L.bv[r] + (v - L.pre[r])];",
                 "                        x[u] = make_uint4(v, v * 3u, v * 5u, v * 7u);")],
 }
 # k_l1_fast (level 1, whole tiles): compute without the point loads, loads
@@ -116,15 +116,15 @@ PATCHES["l1noatom"] = [("hm_kernels.hip", "        if (cnt[q]) gpos[q] = atomicA
 # stores, no emit pass at all (profiles/r6/small_pairs_atomics_ab.jsonl has
 # the round-6 per-wave-reservation results, incl. sharded and non-returning
 # cursor atomics)
-PATCHES["spnoatom"] = [("hm_kernels.hip", "s_base = btotal ? atomicAdd(a.out.cursor, (unsigned long long)btotal) : 0ull;",
+PATCHES["spnoatom"] = [("hm_aggregate.hip", "s_base = btotal ? atomicAdd(a.out.cursor, (unsigned long long)btotal) : 0ull;",
                         "s_base = (unsigned long long)(kb & 0xFFFFFu) * 96u * HM_SPP_WAVES * 64u;")]
 PATCHES["stamps7noatom"] = PATCHES["spnoatom"]
 PATCH_DEFINES["stamps7noatom"] = ["HM_STAMPS=7"]
 # k_small_pairs held to 8 waves per SIMD (<= 96 SGPRs), with 16 rows a round (LDS for 8 blocks)
-PATCHES["sp8w16"] = [("hm_kernels.hip", "__global__ __launch_bounds__(64 * NWB) void k_small_pairs(HmAggArgs a)",
+PATCHES["sp8w16"] = [("hm_aggregate.hip", "__global__ __launch_bounds__(64 * NWB) void k_small_pairs(HmAggArgs a)",
                       "__global__ __launch_bounds__(64 * NWB) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_small_pairs(HmAggArgs a)")]
 PATCH_DEFINES["sp8w16"] = ["HM_SPP_ROWS=16"]
-PATCHES["spnostore"] = [("hm_kernels.hip", "        if (i < n && p < a.out.capacity) {",
+PATCHES["spnostore"] = [("hm_aggregate.hip", "        if (i < n && p < a.out.capacity) {",
                          "        if (i < n && p == 0x123456789ull && p < a.out.capacity) {")]
 # levels 2.. always on the spread plan (3 zooms per level) when no tile is hot
 PATCHES["spreadall"] = [("hm_api.cpp", "spread_replan(ctx->host_aux, F, (double)n, zb, zs, &L, ctx->spread_min_keys, true);",
@@ -160,19 +160,19 @@ PATCHES["rxnolb"] = [("hm_general.hip", """        for (int64_t p = (int64_t)til
                       """        for (int64_t p = (int64_t)tile - 1; p >= 0 && p == 0x7FFFFFFFFFFF;) {
             uint64_t wv[HM_OS_LB];""")]
 # k_aggregate: multi-item buckets without their global histogram adds (timing only)
-PATCHES["agnoslot"] = [("hm_kernels.hip", "            if (i < ncell && x[k]) atomicAdd(&g[i], x[k]);",
+PATCHES["agnoslot"] = [("hm_aggregate.hip", "            if (i < ncell && x[k]) atomicAdd(&g[i], x[k]);",
                         "            if (i < ncell && x[k] == 0xFFFFFFFFu) atomicAdd(&g[i], x[k]);")]
 # hm_count's emit reservations without the cursor atomic (timing only)
-PATCHES["emitnocur"] = [("hm_kernels.hip", "if (lane == NW - 1) *sbase = incl ? atomicAdd(o.cursor, (unsigned long long)incl) : 0ull;",
+PATCHES["emitnocur"] = [("hm_aggregate.hip", "if (lane == NW - 1) *sbase = incl ? atomicAdd(o.cursor, (unsigned long long)incl) : 0ull;",
                          "if (lane == NW - 1) *sbase = (uint64_t)(hm_block_id() & 4095u) * 16384u;"),
-                        ("hm_kernels.hip", "if (threadIdx.x == 0) *sbase = atomicAdd(o.cursor, (unsigned long long)tot);",
+                        ("hm_aggregate.hip", "if (threadIdx.x == 0) *sbase = atomicAdd(o.cursor, (unsigned long long)tot);",
                          "if (threadIdx.x == 0) *sbase = (uint64_t)(hm_block_id() & 4095u) * 16384u;")]
 # the route's scatter without its record stores
 PATCHES["xrnostore"] = [("hm_merge.hip", """            if (OUT == 0) {
                 hm_rec_put(a.rec_out + 5 * q, sk[i], (uint32_t)sc[i]);""", """            if (OUT == 0) {
                 if (q == 0x123456789ull) hm_rec_put(a.rec_out + 5 * q, sk[i], (uint32_t)sc[i]);""")]
 # hm_emit_cells (k_aggregate's pyramid emission) without its cell stores (timing only)
-PATCHES["agnoemit"] = [("hm_kernels.hip", """        if (nz && pos < o.capacity) {
+PATCHES["agnoemit"] = [("hm_aggregate.hip", """        if (nz && pos < o.capacity) {
             o.keys[pos] = k;""", """        if (nz && pos == 0x123456789ull) {
             o.keys[pos] = k;""")]
 # K1 phase-lockstep probe: the first round's second block of a CU starts ~16 us
