@@ -33,6 +33,7 @@ HM_STREAM_ALLTIME = -1
 HM_VIEW_MAX_RECTS, HM_VIEW_MERGED, HM_VIEW_EACH = 32, -1, -2   # hm_stream_view
 HM_STREAM_UNDATED, HM_IMPORT_DISTINCT = 0xFFFFFFFF, 1           # hm_stream_export / hm_stream_import
 HM_RASTER_MAX_TILES, HM_RASTER_MAX_BINS_LOG2, HM_RASTER_MAX_HALO = 64, 8, 8   # hm_*_raster, hm_raster_render
+HM_RASTER_MAX_FRAMES = 1 << 16   # hm_stream_raster_frames
 HM_SCALE_LINEAR, HM_SCALE_LOG = 0, 1
 
 EXPORTS = ["hm_abi_version", "hm_status_string", "hm_ctx_create", "hm_ctx_set_stream", "hm_ctx_destroy", "hm_ctx_tune",
@@ -41,6 +42,7 @@ EXPORTS = ["hm_abi_version", "hm_status_string", "hm_ctx_create", "hm_ctx_set_st
            "hm_stream_create", "hm_stream_add", "hm_stream_cells", "hm_stream_rollup", "hm_stream_extract",
            "hm_stream_window", "hm_stream_view", "hm_stream_expire", "hm_stream_export", "hm_stream_import",
            "hm_stream_destroy", "hm_stream_raster", "hm_cells_raster", "hm_raster_render",
+           "hm_stream_raster_frames", "hm_raster_accumulate",
            "hm_dense_grid_size", "hm_cells_route", "hm_cells_merge", "hm_cells_merge_runs",
            "hm_cells_route_pieces", "hm_cells_merge_pieces", "hm_dense_cells", "hm_format_bins", "hm_format_ids", "hm_bench_read"]
 
@@ -126,6 +128,9 @@ def load() -> ctypes.CDLL:
         L.hm_cells_raster.argtypes = [vp, vp, vp, c.c_int64, P(c.c_int64), c.c_int, c.c_int, c.c_int, vp]
         L.hm_raster_render.argtypes = [vp, vp, c.c_int, c.c_int, c.c_int, c.c_int, c.c_int, c.c_uint64, vp, vp, vp,
                                        P(c.c_uint64)]
+        L.hm_stream_raster_frames.argtypes = [vp, c.c_int64, c.c_int64, c.c_int64, c.c_int64, P(c.c_int64), c.c_int,
+                                              c.c_int, c.c_int, vp]
+        L.hm_raster_accumulate.argtypes = [vp, vp, c.c_int64, c.c_int64, c.c_int64, vp]
         L.hm_dense_grid_size.argtypes = [c.c_int]
         L.hm_dense_grid_size.restype = c.c_int64
         L.hm_cells_route.argtypes = [vp, vp, vp, c.c_int64, c.c_int, c.c_int, c.c_int, vp, vp, vp, c.c_int,

@@ -2410,3 +2410,18 @@ extern "C" int hm_raster_render(hm_ctx* ctx, const uint64_t* grid, int ntiles, i
     if (vmax_used) *vmax_used = a.vs ? a.vs : (uint64_t)down[1];
     return HM_OK;
 }
+
+extern "C" int hm_raster_accumulate(hm_ctx* ctx, const uint64_t* grid_in, int64_t nframes, int64_t frame_elems,
+                                    int64_t window, uint64_t* grid_out)
+{
+    if (!ctx || !grid_in || !grid_out || nframes < 1 || frame_elems < 1 || window < 0 ||
+        nframes > (INT64_MAX / 8) / frame_elems)
+        return HM_E_ARG;
+    const uintptr_t in = (uintptr_t)grid_in, out = (uintptr_t)grid_out, bytes = (uintptr_t)(nframes * frame_elems * 8);
+    if (in < out + bytes && out < in + bytes) return HM_E_ARG;   /* the leaving frame is read after its slot is written */
+    HIPCHK(hipSetDevice(ctx->device));
+    hm_launch_raster_accumulate(ctx->stream, grid_in, grid_out, (uint64_t)nframes, (uint64_t)frame_elems,
+                                (uint64_t)((window == 0 || window > nframes) ? nframes : window));
+    HIPCHK(hipGetLastError());
+    return HM_OK;
+}

@@ -706,9 +706,14 @@ struct HmsRasterArgs {
     uint32_t W;              /* grid side S + 2 halo */
     uint64_t box_lo, box_span;
     unsigned long long* grid;
+    /* frames (k_stream_raster_frames only; hm_stream_frames.h): a cell of hour
+     * offset x goes to the grids at grid + ((x - lo + phase) / fh) * fstride */
+    uint32_t fh, phase;
+    uint64_t fstride;        /* ntiles * W * W */
     HmsRasterRect rects[HMS_RASTER_MAX_TILES];   /* by value (2 KB): wave-uniform, read as scalars */
 };
 void hm_launch_stream_raster(hipStream_t s, const HmsRasterArgs& a);
+void hm_launch_stream_raster_frames(hipStream_t s, const HmsRasterArgs& a);
 /* the same scatter from cells in hm_count's key layout (hm_raster.hip); a
  * tile's grid origin may lie outside the square (oy, ox < 0) */
 struct HmRasterTile {
@@ -742,6 +747,10 @@ struct HmRenderArgs {
 };
 void hm_launch_raster_blur(hipStream_t s, const HmRenderArgs& a);
 void hm_launch_raster_colour(hipStream_t s, const HmRenderArgs& a);
+/* out[f][e] = the sum of in[f - window + 1 .. f][e], frames below 0 left out
+ * (k_raster_accumulate); 1 <= window <= nframes */
+void hm_launch_raster_accumulate(hipStream_t s, const uint64_t* in, uint64_t* out, uint64_t nframes, uint64_t elems,
+                                 uint64_t window);
 
 /* merged label cells -> caller's arrays (k_stream_emit) */
 struct HmsEmitArgs {

@@ -18,6 +18,9 @@
  *                    atomic max per block.
  *   k_raster_colour  B -> level 0..255 (linear, or a piecewise-linear fixed
  *                    point log2) -> the LUT's RGBA word.
+ *
+ * Grids of several frames (hm_stream_raster_frames) are frame-major, so one
+ * frame is a raster as above; k_raster_accumulate sums them along the frames.
  */
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -195,4 +198,45 @@ void hm_launch_raster_colour(hipStream_t s, const HmRenderArgs& a)
 {
     const uint64_t n = (uint64_t)a.ntiles << (2 * a.bins_log2);
     hipLaunchKernelGGL(k_raster_colour, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a);
+}
+
+/* Trailing or cumulative sums along the frames of a frame-major grid
+ * (hm_raster_accumulate): out[f][e] = in[f - window + 1 .. f][e] summed.  The
+ * threads of a wave own consecutive elements e, so every frame's load and
+ * store is one coalesced row; a thread walks the frames with a running sum,
+ * adding the entering frame and subtracting the leaving one (read again from
+ * the input: 16 B read and 8 B written per element, 8 B read while the window
+ * is still filling and throughout a cumulative sum).  HM_ACC_U frames' loads
+ * are issued together.  window: 1 .. nframes (nframes: nothing ever leaves). */
+#define HM_ACC_U 4
+__global__ __launch_bounds__(256) void k_raster_accumulate(const uint64_t* __restrict__ in, uint64_t* __restrict__ out,
+                                                           uint64_t nframes, uint64_t elems, uint64_t window)
+{
+    constexpr int U = HM_ACC_U;
+    for (uint64_t e = (uint64_t)blockIdx.x * 256 + threadIdx.x; e < elems; e += (uint64_t)gridDim.x * 256) {
+        uint64_t sum = 0;
+        for (uint64_t f0 = 0; f0 < nframes; f0 += U) {
+            uint64_t add[U], sub[U];
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+                const uint64_t f = f0 + u;
+                add[u] = f < nframes ? in[f * elems + e] : 0ull;
+                sub[u] = (f < nframes && f >= window) ? in[(f - window) * elems + e] : 0ull;
+            }
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+                const uint64_t f = f0 + u;
+                sum += add[u] - sub[u];
+                if (f < nframes) out[f * elems + e] = sum;
+            }
+        }
+    }
+}
+
+void hm_launch_raster_accumulate(hipStream_t s, const uint64_t* in, uint64_t* out, uint64_t nframes, uint64_t elems,
+                                 uint64_t window)
+{
+    const uint64_t blocks = (elems + 255) / 256;
+    hipLaunchKernelGGL(k_raster_accumulate, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(256), 0, s, in, out,
+                       nframes, elems, window);
 }

@@ -31,6 +31,8 @@
  * the key alone, so merge and emit see the viewport's cells, not the window's.
  * A raster (hm_stream_raster, k_stream_raster) is that filter followed by adds
  * into dense per-tile grids: equal cells meet in one bin, so nothing is merged.
+ * Frames (hm_stream_raster_frames, k_stream_raster_frames) are the same pass
+ * with each survivor sent to the grids of its own hour's frame.
  * Retention (hm_stream_expire, k_stream_expire)
  * filters the log into the alternate arrays and moves the surviving buckets
  * to a fresh bucket table, which frees the slots of the expired hours and of
@@ -639,8 +641,17 @@ __device__ __forceinline__ bool hms_raster_in(const HmsRasterArgs& a, uint64_t b
  * no intern, no ranking and no cursor.  A cell is added to the grid of every
  * tile whose haloed square holds it (the rectangles of neighbour tiles
  * overlap by their halos; a repeated tile is its own grid), one non-returning
- * 64-bit atomic each; the survivors follow the viewport, not the log. */
-__global__ __launch_bounds__(256) void k_stream_raster(HmsRasterArgs a)
+ * 64-bit atomic each; the survivors follow the viewport, not the log.
+ *
+ * FRAMES (hm_stream_raster_frames): the same pass with a time axis.  A
+ * survivor's bucket key holds its hour, so its adds go to the grids of its own
+ * frame, fstride elements apart: one more multiply-add on the address and,
+ * for the survivors only, the division by the wave-uniform frame length (none
+ * when that is 1 hour).  A frame is not a label, so still nothing is interned,
+ * ranked or merged, and the adds of a screen spread over nframes times the
+ * addresses. */
+template <bool FRAMES>
+__device__ __forceinline__ void hms_raster_pass(const HmsRasterArgs& a)
 {
     constexpr int U = HMS_VW_U;
     const int tid = threadIdx.x;
@@ -674,10 +685,18 @@ __global__ __launch_bounds__(256) void k_stream_raster(HmsRasterArgs a)
         hit &= box;
         if (!__ballot(hit != 0)) continue;
         uint32_t sel = 0;             /* bit u: ... of the wanted hours and group */
+        uint32_t fr[U];               /* FRAMES: a survivor's frame, counted from the first clamped hour's */
 #pragma unroll
         for (int u = 0; u < U; u++)
-            if ((hit >> u) & 1u)
-                sel |= (uint32_t)hms_raster_in(a, a.buckets.keys[(k[u] >> a.cb) & a.buckets.mask]) << u;
+            if ((hit >> u) & 1u) {
+                const uint64_t bk = a.buckets.keys[(k[u] >> a.cb) & a.buckets.mask];
+                const bool in = hms_raster_in(a, bk);
+                sel |= (uint32_t)in << u;
+                if (FRAMES && in) {
+                    const uint32_t x = (uint32_t)bk - a.lo + a.phase;
+                    fr[u] = a.fh == 1 ? x : x / a.fh;
+                }
+            }
         if (!__ballot(sel != 0)) continue;
         uint64_t cn[U];
 #pragma unroll
@@ -694,11 +713,16 @@ __global__ __launch_bounds__(256) void k_stream_raster(HmsRasterArgs a)
                 const uint64_t d = (k[u] & cmask) - R.id_lo;
                 const uint32_t c = ((uint32_t)d & zmask) - R.col_lo;
                 if (((sel >> u) & 1u) && d < R.span && c < R.col_w)
-                    atomicAdd(&g[((uint32_t)(d >> R.z) + R.y0) * a.W + c + R.x0], (unsigned long long)cn[u]);
+                    atomicAdd(&g[(FRAMES ? (uint64_t)fr[u] * a.fstride : 0ull) +
+                                 ((uint32_t)(d >> R.z) + R.y0) * a.W + c + R.x0],
+                              (unsigned long long)cn[u]);
             }
         }
     }
 }
+
+__global__ __launch_bounds__(256) void k_stream_raster(HmsRasterArgs a) { hms_raster_pass<false>(a); }
+__global__ __launch_bounds__(256) void k_stream_raster_frames(HmsRasterArgs a) { hms_raster_pass<true>(a); }
 
 /* old-table bucket key of a log cell when it outlives the cut (undated cells
  * have no time and always do), or ~0 */
@@ -1032,6 +1056,13 @@ void hm_launch_stream_raster(hipStream_t s, const HmsRasterArgs& a)
 {
     const uint64_t chunks = (a.n + 256 * HMS_VW_U - 1) / (256 * HMS_VW_U);
     if (a.n) hipLaunchKernelGGL(k_stream_raster, dim3((unsigned)(chunks < 2048 ? chunks : 2048)), dim3(256), 0, s, a);
+}
+
+void hm_launch_stream_raster_frames(hipStream_t s, const HmsRasterArgs& a)
+{
+    const uint64_t chunks = (a.n + 256 * HMS_VW_U - 1) / (256 * HMS_VW_U);
+    if (a.n)
+        hipLaunchKernelGGL(k_stream_raster_frames, dim3((unsigned)(chunks < 2048 ? chunks : 2048)), dim3(256), 0, s, a);
 }
 
 void hm_launch_stream_expire(hipStream_t s, const HmsExpireArgs& a)

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "hm_ctx.h"
+#include "hm_stream_frames.h"
 #include "hm_stream_rect.h"
 
 namespace {
@@ -915,23 +916,12 @@ extern "C" int hm_stream_view(hm_stream* s, int64_t hour_lo, int64_t hour_hi, in
     return stream_merge_emit(s, keys_out, counts_out, groups_out, nullptr, capacity, n_out);
 }
 
-extern "C" int hm_stream_raster(hm_stream* s, int64_t hour_lo, int64_t hour_hi, int64_t group, const int64_t* tiles,
-                                int ntiles, int bins_log2, int halo, uint64_t* grid_out)
+/* a raster's tiles, group and log into the kernel's struct: everything but
+ * its hours and its grid */
+static void stream_raster_fill(const hm_stream* s, int64_t group, const int64_t* tiles, int ntiles, int bins_log2,
+                               int halo, HmsRasterArgs& a)
 {
-    const HourWindow w = stream_hours(s, hour_lo, hour_hi);
-    if (!s || !grid_out || w.kind == HW_INVALID || group < HM_VIEW_MERGED || group > (int64_t)HMS_NOGROUP ||
-        !raster_args_ok(tiles, ntiles, bins_log2, halo, s->zmin, s->zmax))
-        return HM_E_ARG;
-    hm_ctx* ctx = s->ctx;
-    HIPCHK(hipSetDevice(ctx->device));
-    hipStream_t q = ctx->stream;
-    const int64_t S = 1ll << bins_log2, W = S + 2 * halo;
-    HIPCHK(hipMemsetAsync(grid_out, 0, (size_t)ntiles * W * W * 8, q));
-    if (w.kind == HW_EMPTY) return HM_OK;   /* all of it outside the stream's hours */
-    if (s->llen == 0) return HM_OK;
-    HmsRasterArgs a;
-    a.alltime = w.kind == HW_ALLTIME;
-    a.lo = w.lo, a.hi = w.hi;
+    const int64_t W = (1ll << bins_log2) + 2 * halo;
     uint64_t box_hi = 0;
     a.box_lo = ~0ull;
     for (int t = 0; t < ntiles; t++) {
@@ -954,8 +944,58 @@ extern "C" int hm_stream_raster(hm_stream* s, int64_t hour_lo, int64_t hour_hi, 
     a.gmode = group == HM_VIEW_MERGED ? HMS_VIEW_MERGED : HMS_VIEW_GROUP;
     a.group = group >= 0 ? (uint32_t)group : 0u;
     a.W = (uint32_t)W;
+    a.fh = 1, a.phase = 0, a.fstride = 0;
+}
+
+extern "C" int hm_stream_raster(hm_stream* s, int64_t hour_lo, int64_t hour_hi, int64_t group, const int64_t* tiles,
+                                int ntiles, int bins_log2, int halo, uint64_t* grid_out)
+{
+    const HourWindow w = stream_hours(s, hour_lo, hour_hi);
+    if (!s || !grid_out || w.kind == HW_INVALID || group < HM_VIEW_MERGED || group > (int64_t)HMS_NOGROUP ||
+        !raster_args_ok(tiles, ntiles, bins_log2, halo, s->zmin, s->zmax))
+        return HM_E_ARG;
+    hm_ctx* ctx = s->ctx;
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t q = ctx->stream;
+    const int64_t S = 1ll << bins_log2, W = S + 2 * halo;
+    HIPCHK(hipMemsetAsync(grid_out, 0, (size_t)ntiles * W * W * 8, q));
+    if (w.kind == HW_EMPTY) return HM_OK;   /* all of it outside the stream's hours */
+    if (s->llen == 0) return HM_OK;
+    HmsRasterArgs a;
+    stream_raster_fill(s, group, tiles, ntiles, bins_log2, halo, a);
+    a.alltime = w.kind == HW_ALLTIME;
+    a.lo = w.lo, a.hi = w.hi;
     a.grid = (unsigned long long*)grid_out;
     hm_launch_stream_raster(q, a);
+    HIPCHK(hipGetLastError());
+    return HM_OK;
+}
+
+extern "C" int hm_stream_raster_frames(hm_stream* s, int64_t hour_lo, int64_t hour_hi, int64_t frame_hours,
+                                       int64_t group, const int64_t* tiles, int ntiles, int bins_log2, int halo,
+                                       uint64_t* grid_out)
+{
+    HmsFramePlan p;
+    if (!s || !grid_out || (hour_lo == HM_STREAM_ALLTIME && hour_hi == HM_STREAM_ALLTIME) ||
+        hms_frame_plan((int64_t)s->base, hour_lo, hour_hi, frame_hours, HM_RASTER_MAX_FRAMES, &p) ||
+        group < HM_VIEW_MERGED || group > (int64_t)HMS_NOGROUP ||
+        !raster_args_ok(tiles, ntiles, bins_log2, halo, s->zmin, s->zmax))
+        return HM_E_ARG;
+    hm_ctx* ctx = s->ctx;
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t q = ctx->stream;
+    const int64_t W = (1ll << bins_log2) + 2 * halo;
+    const uint64_t fstride = (uint64_t)ntiles * W * W;
+    HIPCHK(hipMemsetAsync(grid_out, 0, (size_t)p.nframes * fstride * 8, q));
+    if (p.lo == p.hi) return HM_OK;         /* all of it outside the stream's hours */
+    if (s->llen == 0) return HM_OK;
+    HmsRasterArgs a;
+    stream_raster_fill(s, group, tiles, ntiles, bins_log2, halo, a);
+    a.alltime = 0;
+    a.lo = p.lo, a.hi = p.hi;
+    a.fh = p.fh, a.phase = p.phase, a.fstride = fstride;
+    a.grid = (unsigned long long*)grid_out + (uint64_t)p.frame0 * fstride;   /* the first clamped hour's frame */
+    hm_launch_stream_raster_frames(q, a);
     HIPCHK(hipGetLastError());
     return HM_OK;
 }

@@ -8,8 +8,11 @@ and hm_raster_render (include/heatmap_amd.h, "Rasters").
 A grid is an int64 CUDA tensor [T, W, W], W = 2^bins_log2 + 2 halo: the bins of
 zoom tz + bins_log2 under tile (tz, tr, tc) with a halo of neighbour bins, so a
 tile blurred alone is seamless with its neighbours.  StreamingHeatmap.tile_raster
-fills the same grids straight from the resident log.  There is no CPU
-fallback: without a device these calls raise DeviceUnavailable.
+fills the same grids straight from the resident log, tile_frames a stack of
+them [F, T, W, W], one per frame of the hours; accumulate sums such frames
+into trailing windows (hm_raster_accumulate) and apng_bytes packs rendered
+frames into an animated PNG.  There is no CPU fallback: without a device these
+calls raise DeviceUnavailable.
 """
 from __future__ import annotations
 
@@ -160,17 +163,77 @@ def render(grid, bins_log2, halo, radius, scale="log", vmax=None, ramp="heat", l
     return (rgba, used.value, lev) if levels else (rgba, used.value)
 
 
+def accumulate(grid, window=0):
+    """int64 CUDA tensor of grid's shape: trailing sums along its first axis,
+    the frames of StreamingHeatmap.tile_frames -- out[f] = grid[max(0, f -
+    window + 1) .. f] summed (modulo 2^64); window = 0 or >= the number of
+    frames: the cumulative sum; window = 1: a copy (hm_raster_accumulate)."""
+    torch = _dv._torch()
+    k = int(window)
+    if k < 0:
+        raise ValueError("window must be 0 (cumulative) or a number of frames (got %r)" % (window,))
+    if not isinstance(grid, torch.Tensor) or grid.dtype != torch.int64 or grid.device.type != "cuda":
+        raise ValueError("grid must be an int64 CUDA tensor (tile_frames)")
+    if grid.dim() < 1 or grid.numel() < 1:
+        raise ValueError("grid must hold at least one frame of at least one element (got %r)" % (tuple(grid.shape),))
+    grid = grid.contiguous()
+    out = torch.empty_like(grid)
+    ctx = _dv.context(grid.device.index)
+    rc = ctx.L.hm_raster_accumulate(ctx.ptr, _dv._ptr(grid), grid.shape[0], grid.numel() // grid.shape[0], k,
+                                    _dv._ptr(out))
+    if rc != _lib.HM_OK:
+        _lib.raise_for(rc)
+    return out
+
+
+def _png_chunk(tag: bytes, data: bytes) -> bytes:
+    return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xFFFFFFFF)
+
+
+def _png_scanlines(a: np.ndarray) -> bytes:
+    """the deflated scanlines of one [H, W, 4] image: filter type 0, then the row's bytes"""
+    hgt, wid = a.shape[:2]
+    raw = np.concatenate([np.zeros((hgt, 1), np.uint8), np.ascontiguousarray(a).reshape(hgt, wid * 4)], axis=1)
+    return zlib.compress(raw.tobytes(), 6)
+
+
 def png_bytes(rgba) -> bytes:
     """An 8-bit RGBA PNG of one [H, W, 4] uint8 image (numpy array or tensor)."""
     a = rgba.cpu().numpy() if hasattr(rgba, "cpu") else np.asarray(rgba)
     if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 4 or a.shape[0] < 1 or a.shape[1] < 1:
         raise ValueError("png_bytes takes one uint8 [H, W, 4] image (got %s %r)" % (a.dtype, a.shape))
     hgt, wid = a.shape[:2]
-    # every scanline: filter type 0, then the row's bytes
-    raw = np.concatenate([np.zeros((hgt, 1), np.uint8), np.ascontiguousarray(a).reshape(hgt, wid * 4)], axis=1)
+    return (b"\x89PNG\r\n\x1a\n" + _png_chunk(b"IHDR", struct.pack(">IIBBBBB", wid, hgt, 8, 6, 0, 0, 0)) +
+            _png_chunk(b"IDAT", _png_scanlines(a)) + _png_chunk(b"IEND", b""))
 
-    def chunk(tag: bytes, data: bytes) -> bytes:
-        return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xFFFFFFFF)
 
-    return (b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", wid, hgt, 8, 6, 0, 0, 0)) +
-            chunk(b"IDAT", zlib.compress(raw.tobytes(), 6)) + chunk(b"IEND", b""))
+def apng_bytes(frames_rgba, delay_ms=100, loops=0) -> bytes:
+    """An animated PNG of [F, H, W, 4] uint8 frames (numpy array or tensor:
+    one tile of StreamingHeatmap.tile_frame_images), each shown delay_ms
+    milliseconds, played `loops` times (0: for ever).  IHDR, acTL, then per
+    frame an fcTL and the frame's data -- IDAT for the first, so a viewer
+    without APNG shows that one, fdAT for the others -- under consecutive
+    sequence numbers, IEND."""
+    a = frames_rgba.cpu().numpy() if hasattr(frames_rgba, "cpu") else np.asarray(frames_rgba)
+    if a.dtype != np.uint8 or a.ndim != 4 or a.shape[3] != 4 or min(a.shape[:3]) < 1:
+        raise ValueError("apng_bytes takes uint8 [F, H, W, 4] frames (got %s %r)" % (a.dtype, a.shape))
+    delay, plays = int(delay_ms), int(loops)
+    if not 0 <= delay <= 0xFFFF:
+        raise ValueError("delay_ms must be 0..65535 (got %r)" % (delay_ms,))
+    if not 0 <= plays <= 0x7FFFFFFF:
+        raise ValueError("loops must be 0 (for ever) or a number of plays (got %r)" % (loops,))
+    nf, hgt, wid = a.shape[:3]
+    out = [b"\x89PNG\r\n\x1a\n", _png_chunk(b"IHDR", struct.pack(">IIBBBBB", wid, hgt, 8, 6, 0, 0, 0)),
+           _png_chunk(b"acTL", struct.pack(">II", nf, plays))]
+    seq = 0
+    for f in range(nf):
+        # the whole canvas at (0, 0), delay / 1000 s, dispose: none, blend: source
+        out.append(_png_chunk(b"fcTL", struct.pack(">IIIIIHHBB", seq, wid, hgt, 0, 0, delay, 1000, 0, 0)))
+        seq += 1
+        if f == 0:
+            out.append(_png_chunk(b"IDAT", _png_scanlines(a[f])))
+        else:
+            out.append(_png_chunk(b"fdAT", struct.pack(">I", seq) + _png_scanlines(a[f])))
+            seq += 1
+    out.append(_png_chunk(b"IEND", b""))
+    return b"".join(out)

@@ -24,7 +24,13 @@ label is a device rollup of the hour buckets:
                                (hm_stream_raster: the same filter pass, no
                                merge), and tile_images(...) the same blurred,
                                scaled and coloured into RGBA (heatmap_amd.raster)
-  expire(before_hour)          retention: the cells of hours < before_hour
+  tile_frames(tiles, hours, frame_hours)  the same grids per frame of the hours,
+                               for a time slider or an animation, in ONE pass
+                               (hm_stream_raster_frames); trailing windows or
+                               growth through hm_raster_accumulate;
+                               tile_series(...) the tiles' points per frame and
+                               tile_frame_images(...) the frames on one scale
+  expire(before_hour)         retention: the cells of hours < before_hour
                                leave the stream, their buckets are freed
   snapshot() / save(path)      the whole state as arrays (hm_stream_export: one
                                record per (group, hour, cell)), and back:
@@ -164,6 +170,28 @@ def _raster_args(zmin: int, zmax: int, index: dict, tiles, hours, user, bins_log
     else:
         gw = index.get(user)
     return tiles, lo, hi, gw, b, h
+
+
+def _frame_args(lo: int, hi: int, frame_hours, trailing):
+    """Validated (frame_hours, lead, window) of StreamingHeatmap.tile_frames
+    over the hours [lo, hi): `lead` frames are queried before lo and dropped
+    after the sums, `window` is raster.accumulate's (None: disjoint frames,
+    no sums).  Pure: needs no device."""
+    fh = int(frame_hours)
+    if fh < 1:
+        raise ValueError("frame_hours must be at least 1 (got %r)" % (frame_hours,))
+    if trailing is None:
+        lead, window = 0, None
+    elif trailing == "all":
+        lead, window = 0, 0
+    elif isinstance(trailing, (int, np.integer)) and not isinstance(trailing, bool) and trailing >= 1:
+        lead, window = int(trailing) - 1, int(trailing)
+    else:
+        raise ValueError("trailing must be None, 'all' or a number of frames >= 1 (got %r)" % (trailing,))
+    nf = -((lo - hi) // fh) + lead
+    if nf > _lib.HM_RASTER_MAX_FRAMES:
+        raise ValueError("%d frames; one call takes at most %d" % (nf, _lib.HM_RASTER_MAX_FRAMES))
+    return fh, lead, window
 
 
 def _cells_subset(cells: "_hm.Cells", m: np.ndarray) -> "_hm.Cells":
@@ -736,6 +764,72 @@ class StreamingHeatmap:
         _raster.check_render(bins_log2, radius, radius, scale, vmax)
         grid = self.tile_raster(tiles, hours, user, bins_log2, halo=radius)
         return _raster.render(grid, bins_log2, radius, radius, scale, vmax, ramp)[0]
+
+    def tile_frames(self, tiles, hours, frame_hours=1, user=None, bins_log2=5, halo=0, trailing=None):
+        """int64 CUDA tensor [F, T, W, W]: tile_raster with a time axis, for a
+        time slider or an animation, in ONE pass over the log
+        (hm_stream_raster_frames) instead of one per frame.  hours = (lo, hi)
+        is cut into F = ceil((hi - lo) / frame_hours) frames anchored at lo;
+        frame f holds the hours [lo + f fh, lo + (f + 1) fh), the last one up
+        to hi.  Undated points are in no frame.
+
+        trailing = k (an int >= 1): frame f holds the k frame lengths that END
+        with it, the hours [lo + (f + 1 - k) fh, lo + (f + 1) fh) -- "the
+        trailing 24 hours, advancing hourly" is frame_hours = 1, trailing =
+        24.  The frames are queried from lo - (k - 1) fh on, summed with
+        raster.accumulate(window = k) and the first k - 1 dropped, so every
+        returned frame is a whole window.  trailing = 'all': frame f holds
+        [lo, lo + (f + 1) fh), the growth since lo."""
+        torch = self._torch
+        self.ctx.bind_stream()
+        if hours is None:
+            raise ValueError("frames need hours = (lo, hi): alltime has no first frame")
+        tiles, lo, hi, gw, b, h = _raster_args(self.zmin, self.zmax, self._index, tiles, hours, user, bins_log2, halo)
+        fh, lead, window = _frame_args(lo, hi, frame_hours, trailing)
+        nf = -((lo - lead * fh - hi) // fh)
+        w = (1 << b) + 2 * h
+        dev = "cuda:%d" % self.device_index
+        if gw is None:
+            return torch.zeros((nf - lead, len(tiles), w, w), dtype=torch.int64, device=dev)
+        grid = torch.empty((nf, len(tiles), w, w), dtype=torch.int64, device=dev)
+        for j in range(0, len(tiles), _lib.HM_RASTER_MAX_TILES):
+            part = tiles[j:j + _lib.HM_RASTER_MAX_TILES]
+            # a call's frames are contiguous [nf][its tiles]: parts are joined along T
+            g = grid if len(part) == len(tiles) else torch.empty((nf, len(part), w, w), dtype=torch.int64, device=dev)
+            rc = self.ctx.L.hm_stream_raster_frames(self.ptr, lo - lead * fh, hi, fh, gw, _raster._tile_array(part),
+                                                    len(part), b, h, device._ptr(g))
+            _lib.raise_for(rc)
+            if g is not grid:
+                grid[:, j:j + len(part)] = g
+        if window is None:
+            return grid
+        return _raster.accumulate(grid, window)[lead:]
+
+    def tile_series(self, tiles, hours, frame_hours=1, user=None):
+        """int64 CUDA tensor [F, T]: the kept points inside each tile (tz, tr,
+        tc) per frame of hours = (lo, hi) -- a per-hour chart; a viewport's
+        series is the sum over its covering tiles.  tile_frames with bins_log2
+        = 0, where a tile's grid is its own cell: no kernel of its own."""
+        return self.tile_frames(tiles, hours, frame_hours, user, bins_log2=0, halo=0)[:, :, 0, 0]
+
+    def tile_frame_images(self, tiles, hours, frame_hours=1, user=None, bins_log2=8, radius=2, scale="log", vmax=None,
+                          ramp="heat", trailing=None):
+        """uint8 CUDA tensor [F, T, S, S, 4]: the frames of tile_frames (halo
+        = radius) as RGBA images, every frame on ONE scale so the animation
+        does not flicker.  vmax = None finds that scale in two render passes:
+        every frame is rendered once on its own to read back its largest
+        blurred value vs (in units of 2^-(4 radius)); the largest of them is
+        rounded up to a whole count, vmax = ceil(vs / 2^(4 radius)), and every
+        frame is rendered again with that fixed vmax.  raster.apng_bytes turns
+        one tile's frames, [:, t], into an animated PNG."""
+        b, h, r, _, _ = _raster.check_render(bins_log2, radius, radius, scale, vmax)
+        grid = self.tile_frames(tiles, hours, frame_hours, user, b, halo=r, trailing=trailing)
+        step = _lib.HM_RASTER_MAX_TILES
+        if vmax is None:
+            vs = max(_raster.render(grid[f, j:j + step], b, r, r, scale, None, ramp)[1]
+                     for f in range(grid.shape[0]) for j in range(0, grid.shape[1], step))
+            vmax = max(1, -(-vs >> (4 * r)))
+        return self._torch.stack([_raster.render(grid[f], b, r, r, scale, vmax, ramp)[0] for f in range(grid.shape[0])])
 
     def expire(self, before_hour: int):
         """Retention: drop the cells of every hour < before_hour (undated

@@ -421,8 +421,44 @@ int hm_stream_destroy(hm_stream* s);
  *                     log2(1 + count) with 8 fractional bits.  Pixel = the four
  *                     bytes of lut[level] (device u32[256], bytes R, G, B, A);
  *                     rgba_out: device u8[ntiles][S][S][4], 4-byte aligned;
- *                     levels_out: device u8[ntiles][S][S] or NULL.  Waits once. */
+ *                     levels_out: device u8[ntiles][S][S] or NULL.  Waits once.
+ *   Frames: the same rasters with a time axis, for a time slider, an animation
+ *   or a per-hour chart, in ONE pass over the log instead of one per frame.
+ *   hm_stream_raster_frames  the hours [hour_lo, hour_hi) cut into frames of
+ *                     frame_hours anchored at hour_lo (not at the stream's base
+ *                     hour, and not at a clamped bound: hour_lo may lie below
+ *                     the base and hour_hi beyond the stream's hours; the last
+ *                     frame may be shorter): nframes = ceil((hour_hi - hour_lo)
+ *                     / frame_hours), and a dated cell of hour h, hour_lo <= h <
+ *                     hour_hi, goes to frame (h - hour_lo) / frame_hours.
+ *                     grid_out is device u64[nframes][ntiles][W][W], frame
+ *                     major: frame f is the contiguous [ntiles][W][W] block at
+ *                     element f * ntiles * W * W (64-bit offsets), a raster as
+ *                     above that hm_raster_render takes as it is.  Within a
+ *                     frame every rule of hm_stream_raster holds; undated
+ *                     cells have no hour and are in no frame.  With bins_log2
+ *                     = 0 and halo = 0 a tile's grid is its own cell, and
+ *                     grid_out is the time series u64[nframes][ntiles].  The
+ *                     call zeroes all of grid_out.  HM_E_ARG, grid_out
+ *                     untouched: what hm_stream_raster refuses, frame_hours <
+ *                     1, the HM_STREAM_ALLTIME pair, hour_hi <= hour_lo, more
+ *                     than HM_RASTER_MAX_FRAMES frames.  A window without a
+ *                     cell is HM_OK with an all-zero grid.  The log is left
+ *                     exactly as it is (a frame is not a label: no bucket is
+ *                     interned, nothing is merged); asynchronous.
+ *   hm_raster_accumulate  trailing or cumulative sums along the frames of
+ *                     such a grid (device u64[nframes][frame_elems]):
+ *                     out[f][e] = the sum of in[g][e], max(0, f - window + 1)
+ *                     <= g <= f, modulo 2^64; window = 0 or >= nframes: the
+ *                     cumulative sum; window = 1: a copy.  "The trailing 24
+ *                     hours, advancing hourly" is one scatter of hourly frames
+ *                     and one such pass, not 24 times the atomics.  HM_E_ARG,
+ *                     grid_out untouched: a null pointer, nframes < 1,
+ *                     frame_elems < 1, window < 0, output and input ranges
+ *                     that overlap (grid_out == grid_in included).
+ *                     Asynchronous. */
 #define HM_RASTER_MAX_TILES 64
+#define HM_RASTER_MAX_FRAMES (1 << 16)
 #define HM_RASTER_MAX_BINS_LOG2 8     /* 256 x 256 bins per tile */
 #define HM_RASTER_MAX_HALO 8
 #define HM_SCALE_LINEAR 0
@@ -434,6 +470,10 @@ int hm_cells_raster(hm_ctx* ctx, const uint64_t* keys, const uint64_t* counts, i
 int hm_raster_render(hm_ctx* ctx, const uint64_t* grid, int ntiles, int bins_log2, int halo, int radius,
                      int scale, uint64_t vmax, const uint32_t* lut, uint8_t* rgba_out, uint8_t* levels_out,
                      uint64_t* vmax_used);
+int hm_stream_raster_frames(hm_stream* s, int64_t hour_lo, int64_t hour_hi, int64_t frame_hours, int64_t group,
+                            const int64_t* tiles, int ntiles, int bins_log2, int halo, uint64_t* grid_out);
+int hm_raster_accumulate(hm_ctx* ctx, const uint64_t* grid_in, int64_t nframes, int64_t frame_elems,
+                         int64_t window, uint64_t* grid_out);
 
 /* Multi-GPU exchange of hm_count cells (one process per GPU; the collectives
  * are RCCL calls made by the caller, heatmap_amd/multigpu.py).  They replace

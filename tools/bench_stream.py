@@ -67,6 +67,25 @@ densified in numpy.  --view-only times the views alone (nothing newer than
 hm_stream_view is needed, so a checkout of the parent commit can run it);
 --parent-json FILE puts that run's view times into this one's result as
 "parent_view_ms".
+
+    python tools/bench_stream.py --retain 24 --batches 30 --warmup 0 --frames --out profiles/stream_frames.json
+
+--frames: on the steady retained log, --raster's 4 x 3-tile screen of 256 x
+256 zoom-18 bins with halo 2 as 24 hourly frames over the last 24 hours: one
+hm_stream_raster_frames call ("frames_ms"), the same call with bins_log2 = 0
+(the 12 tiles' hourly series, "series_ms"), hm_raster_accumulate with window =
+6 over the frames and the render of all 24 frames (24 hm_raster_render calls),
+against the only way there was before -- 24 hm_stream_raster calls, one per
+hour ("loop_ms") -- and one hm_stream_raster of the whole window
+("one_raster_pass_ms"); all interleaved in one process, 15 repetitions each,
+host ms around the call(s) plus a synchronise, median and range.  "check":
+every frame equals the hm_stream_raster grid of its hour, the series equal
+the frames' interiors summed, the accumulated frames equal torch's.  The
+accumulate is also given as GB/s over the bytes it must move (8 B read and 8 B
+written per element), next to "read_stream_GBps".  --loop-only times the two
+hm_stream_raster items alone (nothing newer is needed, so a checkout of the
+parent commit can run it); --parent-json FILE puts that run's times into this
+one's result as "parent_loop_ms" and "parent_one_raster_pass_ms".
 """
 import argparse
 import json
@@ -291,6 +310,107 @@ def raster_bench(s, a, lo, hi):
     return out
 
 
+FRAMES = 24
+
+
+def frames_bench(s, a, hi):
+    """--frames (module docstring) on the stream as it stands: the hours [hi - 24, hi)"""
+    import ctypes
+
+    from heatmap_amd import _lib, raster
+
+    lo = hi - FRAMES
+    n, keys, counts, _ = s.window_device(lo, hi)
+    k, cnt = keys[:n], counts[:n]
+    heavy = int(k[torch.argmax(torch.where((k >> 58) == 18, cnt, torch.full_like(cnt, -1)))].item())
+    del keys, counts, k, cnt
+    tr, tc = (((heavy >> 29) & 0x1FFFFFFF) >> 8) - 1, ((heavy & 0x1FFFFFFF) >> 8) - 1
+    tiles = [(10, tr + i, tc + j) for i in range(3) for j in range(4)]
+    b, h, radius, window = 8, 2, 2, 6
+    w, side, nt = (1 << b) + 2 * h, 1 << b, len(tiles)
+    L, ta = s.ctx.L, raster._tile_array(tiles)
+    out = {"hours": [lo, hi], "frames": FRAMES, "frame_hours": 1, "reps": VIEW_REPS, "log_cells": s.cells()[0],
+           "window_cells": n, "tiles": [list(t) for t in tiles], "bins_log2": b, "halo": h,
+           "timing": "host ms around the call(s) plus one synchronise; every timed item interleaved in one process"}
+    loop_grid = torch.empty((FRAMES, nt, w, w), dtype=torch.int64, device="cuda")
+
+    def do_loop():          # the only way there was: one hm_stream_raster call, one pass over the log, per hour
+        for f in range(FRAMES):
+            rc = L.hm_stream_raster(s.ptr, lo + f, lo + f + 1, _lib.HM_VIEW_MERGED, ta, nt, b, h,
+                                    loop_grid[f].data_ptr())
+            assert rc == 0, rc
+
+    def do_pass():          # one raster of the whole window: what one pass over this log costs
+        rc = L.hm_stream_raster(s.ptr, lo, hi, _lib.HM_VIEW_MERGED, ta, nt, b, h, loop_grid[0].data_ptr())
+        assert rc == 0, rc
+
+    timed = {"loop_ms": do_loop, "one_raster_pass_ms": do_pass}
+    if not a.loop_only:
+        grid = torch.empty((FRAMES, nt, w, w), dtype=torch.int64, device="cuda")
+        acc = torch.empty_like(grid)
+        series = torch.empty((FRAMES, nt), dtype=torch.int64, device="cuda")
+        rgba = torch.empty((FRAMES, nt, side, side, 4), dtype=torch.uint8, device="cuda")
+        lut = raster._lut("heat", torch, grid.device)
+        used = ctypes.c_uint64(0)
+
+        def do_frames():
+            rc = L.hm_stream_raster_frames(s.ptr, lo, hi, 1, _lib.HM_VIEW_MERGED, ta, nt, b, h, grid.data_ptr())
+            assert rc == 0, rc
+
+        def do_series():
+            rc = L.hm_stream_raster_frames(s.ptr, lo, hi, 1, _lib.HM_VIEW_MERGED, ta, nt, 0, 0, series.data_ptr())
+            assert rc == 0, rc
+
+        def do_acc():
+            rc = L.hm_raster_accumulate(s.ctx.ptr, grid.data_ptr(), FRAMES, nt * w * w, window, acc.data_ptr())
+            assert rc == 0, rc
+
+        def do_render():    # one render pass: every frame on its own scale (a shared scale is a second such pass)
+            for f in range(FRAMES):
+                rc = L.hm_raster_render(s.ctx.ptr, grid[f].data_ptr(), nt, b, h, radius, _lib.HM_SCALE_LOG, 0,
+                                        lut.data_ptr(), rgba[f].data_ptr(), None, ctypes.byref(used))
+                assert rc == 0, rc
+
+        do_frames()         # the accumulate and the render read its grid
+        timed.update({"frames_ms": do_frames, "series_ms": do_series, "accumulate_ms": do_acc, "render_ms": do_render})
+    for f in timed.values():    # warm: code objects
+        f()
+    t = {name: [] for name in timed}
+    for _ in range(VIEW_REPS):
+        for name, f in timed.items():
+            t[name].append(_ms(f)[0])
+    out.update({name: _stats(x) for name, x in t.items()})
+    do_loop()               # do_pass wrote over frame 0
+    torch.cuda.synchronize()
+    out["grid_sum"] = int(loop_grid.sum())
+    if not a.loop_only:
+        do_frames()
+        do_series()
+        do_acc()
+        torch.cuda.synchronize()
+        same = out["grid_sum"] > 0 and all(bool(torch.equal(grid[f], loop_grid[f])) for f in range(FRAMES))
+        # a tile's series is its grid's interior summed: the 256 x 256 bins of zoom 18 are the tile's zoom-10 cell
+        same &= bool(torch.equal(series, grid[:, :, h:h + side, h:h + side].sum(dim=(2, 3))))
+        csum = torch.cumsum(grid, dim=0)
+        csum[window:] -= csum[:-window].clone()
+        same &= bool(torch.equal(acc, csum))
+        nbytes = 16 * grid.numel()
+        out.update({"check": "ok" if same else "FAIL", "frames_equal_the_loops_grids": same,
+                    "accumulate_window": window, "accumulate_min_bytes": nbytes,
+                    "accumulate_min_bytes_note": "8 B read and 8 B written per element; the kernel reads the leaving "
+                                                 "frame again: 8 B more for the frames past the window",
+                    "accumulate_GBps_over_min_bytes": nbytes / (out["accumulate_ms"]["median"] * 1e-3) / 1e9,
+                    "series_sum": int(series.sum()), "pixels_drawn": int((rgba[..., 3] != 0).sum())})
+    if a.parent_json:
+        pj = json.load(open(a.parent_json))["frames"]
+        assert pj["log_cells"] == out["log_cells"] and pj["grid_sum"] == out["grid_sum"] and pj["tiles"] == out["tiles"]
+        out["parent_loop_ms"] = pj["loop_ms"]
+        out["parent_one_raster_pass_ms"] = pj["one_raster_pass_ms"]
+        out["parent_note"] = ("this script with --frames --loop-only run by a checkout of the parent commit (its "
+                              "library and package) on the same seeded log, in the same session")
+    return out
+
+
 SNAP_REPS = 7
 READD_REPS = 3
 
@@ -431,6 +551,7 @@ def retain(a):
     view = view_bench(s, a, BASE + total - 1 - H, BASE + total) if a.view else None
     snap = snapshot_bench(s, a, lat, lon, list(range(total - 1 - H, total))) if a.snapshot or a.readd_only else None
     ras = raster_bench(s, a, BASE + total - 1 - H, BASE + total) if a.raster else None
+    fra = frames_bench(s, a, BASE + total) if a.frames else None
     result = json.dumps({
         "metric": "stream under retention: expire(newest - H) and window(newest - H, newest + 1) per one-hour batch",
         "retain_hours": H, "batch_points": n, "batches": a.batches, "warmup": a.warmup, "zooms": [a.zmin, a.zmax],
@@ -446,6 +567,7 @@ def retain(a):
         "view": view,
         "snapshot": snap,
         "raster": ras,
+        "frames": fra,
         "series": series,
         "data": "synthetic (heatmap_amd.synth, generated on device, resident in HBM)"})
     print(result)
@@ -477,12 +599,17 @@ def main():
                     help="with --retain: tile rasters and rendered tiles vs views of the same rectangles (module "
                          "docstring)")
     ap.add_argument("--view-only", action="store_true", help="with --raster: time the views alone")
+    ap.add_argument("--frames", action="store_true",
+                    help="with --retain 24 or more: 24 hourly frames of a screen in one call vs one raster call per "
+                         "hour (module docstring)")
+    ap.add_argument("--loop-only", action="store_true", help="with --frames: time the per-hour raster calls alone")
     ap.add_argument("--readd-only", action="store_true",
                     help="with --retain: time only the re-adding of the retained batches to a fresh stream")
     ap.add_argument("--parent-json", default=None, metavar="FILE",
                     help="with --view: a --window-only result of the parent commit, kept as parent_window; with "
                          "--snapshot: its --readd-only result, kept as parent_readd_ms; with --raster: its "
-                         "--view-only result, kept as parent_view_ms")
+                         "--view-only result, kept as parent_view_ms; with --frames: its --loop-only result, kept as "
+                         "parent_loop_ms")
     ap.add_argument("--out", default=None, metavar="FILE", help="with --retain: also write the JSON line to FILE")
     a = ap.parse_args()
     if a.retain > 0:
