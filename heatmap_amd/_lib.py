@@ -34,6 +34,7 @@ HM_VIEW_MAX_RECTS, HM_VIEW_MERGED, HM_VIEW_EACH = 32, -1, -2   # hm_stream_view
 HM_STREAM_UNDATED, HM_IMPORT_DISTINCT = 0xFFFFFFFF, 1           # hm_stream_export / hm_stream_import
 HM_RASTER_MAX_TILES, HM_RASTER_MAX_BINS_LOG2, HM_RASTER_MAX_HALO = 64, 8, 8   # hm_*_raster, hm_raster_render
 HM_RASTER_MAX_FRAMES = 1 << 16   # hm_stream_raster_frames
+HM_SELECT_MAX_GROUPS = 1 << 20   # hm_stream_forget / hm_stream_export_select
 HM_SCALE_LINEAR, HM_SCALE_LOG = 0, 1
 
 EXPORTS = ["hm_abi_version", "hm_status_string", "hm_ctx_create", "hm_ctx_set_stream", "hm_ctx_destroy", "hm_ctx_tune",
@@ -42,7 +43,7 @@ EXPORTS = ["hm_abi_version", "hm_status_string", "hm_ctx_create", "hm_ctx_set_st
            "hm_stream_create", "hm_stream_add", "hm_stream_cells", "hm_stream_rollup", "hm_stream_extract",
            "hm_stream_window", "hm_stream_view", "hm_stream_expire", "hm_stream_export", "hm_stream_import",
            "hm_stream_destroy", "hm_stream_raster", "hm_cells_raster", "hm_raster_render",
-           "hm_stream_raster_frames", "hm_raster_accumulate",
+           "hm_stream_raster_frames", "hm_raster_accumulate", "hm_stream_forget", "hm_stream_export_select",
            "hm_dense_grid_size", "hm_cells_route", "hm_cells_merge", "hm_cells_merge_runs",
            "hm_cells_route_pieces", "hm_cells_merge_pieces", "hm_dense_cells", "hm_format_bins", "hm_format_ids", "hm_bench_read"]
 
@@ -123,6 +124,9 @@ def load() -> ctypes.CDLL:
         L.hm_stream_expire.argtypes = [vp, c.c_int64, P(c.c_int64), P(c.c_int64)]
         L.hm_stream_export.argtypes = [vp, vp, vp, vp, vp, c.c_int64, P(c.c_int64)]
         L.hm_stream_import.argtypes = [vp, vp, vp, vp, vp, c.c_int64, c.c_int]
+        L.hm_stream_forget.argtypes = [vp, P(c.c_uint32), c.c_int64, c.c_int64, c.c_int64, P(c.c_int64), P(c.c_int64)]
+        L.hm_stream_export_select.argtypes = [vp, P(c.c_uint32), c.c_int64, c.c_int64, c.c_int64, vp, vp, vp, vp,
+                                              c.c_int64, P(c.c_int64)]
         L.hm_stream_destroy.argtypes = [vp]
         L.hm_stream_raster.argtypes = [vp, c.c_int64, c.c_int64, c.c_int64, P(c.c_int64), c.c_int, c.c_int, c.c_int, vp]
         L.hm_cells_raster.argtypes = [vp, vp, vp, c.c_int64, P(c.c_int64), c.c_int, c.c_int, c.c_int, vp]

@@ -100,6 +100,7 @@ enum {
     B_MB_KEYS2, B_MB_COUNTS2, B_KEYS_C, B_HOT_FORCE, B_C2B, B_SEG2, B_CTOT, B_CBASE, B_CCUR, B_MG_PIECES,
     B_L1_SLOT,
     B_RS_B, B_RS_MX,   /* hm_raster_render: blurred counts, the two maxima */
+    B_SEL_IDS, B_SEL_MAP,   /* a stream selection: the sorted group ids, the word per bucket slot */
     B_COUNT
 };
 

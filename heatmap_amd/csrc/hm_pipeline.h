@@ -650,6 +650,39 @@ struct HmsExpireArgs {
     unsigned long long* cursor;   /* cells kept */
     unsigned long long* state;    /* HMS_ST_BUCKETS: slots claimed in new_buckets */
 };
+/* A selection of raw (group, hour) buckets (hm_stream_forget,
+ * hm_stream_export_select), judged once per bucket slot, not per cell
+ * (k_stream_select): remap[slot] = HMS_DROP for a selected bucket.  For a
+ * forget the others are moved to a fresh table on the way and remap[slot] is
+ * their slot there (label buckets and empty slots: HMS_DROP, no log cell names
+ * them); for an export (new_buckets.keys == NULL) it is 0. */
+#define HMS_DROP 0xFFFFFFFFu
+struct HmsSelectArgs {
+    HmsBuckets old_buckets;
+    HmsBuckets new_buckets;  /* same capacity, empty; keys NULL: verdicts only */
+    const uint32_t* ids;     /* the groups, sorted and distinct; NULL: every group */
+    uint32_t nids;
+    int alltime;             /* every hour, and the undated buckets */
+    uint32_t lo, hi;         /* else the dated buckets with lo <= hour - base < hi */
+    uint32_t* remap;         /* one word per slot of old_buckets */
+    unsigned long long* state;    /* HMS_ST_BUCKETS: slots claimed in new_buckets */
+};
+void hm_launch_stream_select(hipStream_t s, const HmsSelectArgs& a);
+/* the log's cells of the buckets not dropped, re-keyed through remap
+ * (k_stream_forget: k_stream_expire's pass with one 4-byte gather per cell) */
+struct HmsForgetArgs {
+    const uint64_t* keys;    /* the log */
+    const uint64_t* counts;
+    uint64_t n;
+    const uint32_t* remap;   /* old bucket -> new bucket or HMS_DROP */
+    uint64_t mask;           /* bucket slots - 1 */
+    int cb;
+    uint64_t* keys_out;      /* new bucket << cb | cell */
+    uint64_t* counts_out;
+    unsigned long long* cursor;   /* cells kept */
+};
+void hm_launch_stream_forget(hipStream_t s, const HmsForgetArgs& a);
+
 /* a viewport query: the log's cells inside any of a few rectangles, of the
  * window's hours and the wanted group(s), re-keyed to label buckets
  * (k_stream_view).  A rectangle (zoom z, rows [row_lo, row_hi), cols [col_lo,
@@ -765,6 +798,16 @@ struct HmsEmitArgs {
     uint32_t* groups_out;
     uint32_t* periods_out;
 };
+/* the log's cells of the selected buckets -> caller's arrays, compacted
+ * (k_stream_export_select): *cursor counts every selected cell, the first
+ * `capacity` of them are written */
+struct HmsExportSelArgs {
+    HmsEmitArgs e;           /* the log and the outputs, as k_stream_export's */
+    const uint32_t* verdict; /* per bucket slot: HMS_DROP = selected (k_stream_select) */
+    uint64_t capacity;
+    unsigned long long* cursor;
+};
+void hm_launch_stream_export_select(hipStream_t s, const HmsExportSelArgs& a);
 /* pre-aggregated cells appended at the log's tail (k_stream_import) */
 struct HmsImportArgs {
     const uint64_t* keys;    /* hm_count layout */

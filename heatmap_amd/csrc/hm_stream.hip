@@ -36,7 +36,11 @@
  * Retention (hm_stream_expire, k_stream_expire)
  * filters the log into the alternate arrays and moves the surviving buckets
  * to a fresh bucket table, which frees the slots of the expired hours and of
- * every rollup label.  The state leaves and enters as cells: hm_stream_export
+ * every rollup label.  Forgetting (hm_stream_forget) is the same move for a
+ * selection of (group, hour) buckets: k_stream_select judges every bucket slot
+ * once and moves the buckets that stay, k_stream_forget filters the log through
+ * the slot map it leaves; hm_stream_export_select lists the selected cells
+ * instead (k_stream_export_select).  The state leaves and enters as cells: hm_stream_export
  * lists the compacted log with each cell's group and hour (k_stream_export,
  * one pass), hm_stream_import appends such cells at the tail under interned
  * buckets (k_stream_import: a snapshot restored, another stream merged in).
@@ -48,6 +52,8 @@
 #include "hm_device.h"
 #include "hm_pipeline.h"
 #include "hm_table.h"
+#define HMS_SELECT_FN __device__ __forceinline__   /* hms_select_has on the device */
+#include "hm_stream_select.h"
 
 __device__ __forceinline__ uint64_t hms_pyr_off(int z) { return ((1ull << (2 * z)) - 1ull) / 3ull; }
 
@@ -832,6 +838,179 @@ __global__ __launch_bounds__(256) void k_stream_expire(HmsExpireArgs a)
     }
 }
 
+/* A selection judged per bucket, not per cell (hm_stream_forget,
+ * hm_stream_export_select): whether a cell is selected depends on its bucket's
+ * (group, period) alone, so one thread per slot of the bucket table decodes the
+ * key, tests the hours and finds the group among the sorted ids by binary
+ * search (about 20 L2-resident steps at 2^20 ids), and the passes over the log
+ * only gather the word written here.  Rollup labels hold no log cells and are
+ * never selected.  For a forget the thread also moves its bucket, when that
+ * stays, to the fresh table (distinct keys: one CAS each on its own word) and
+ * leaves the new slot as the verdict, so the log pass needs no probe: every
+ * unselected raw bucket is carried over, with or without cells in the log. */
+__global__ __launch_bounds__(256) void k_stream_select(HmsSelectArgs a)
+{
+    const uint64_t nb = a.old_buckets.mask + 1;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    uint32_t bclaimed = 0, full = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nb; i += stride) {
+        const uint64_t bk = a.old_buckets.keys[i];
+        const uint32_t pw = (uint32_t)bk, g = (uint32_t)(bk >> 32);
+        const bool dated = (pw >> 28) == 0;
+        const bool raw = bk != HMS_EMPTY && (dated || pw == HMS_UNDATED);
+        const bool hours = a.alltime ? raw : (dated && pw >= a.lo && pw < a.hi);
+        const bool sel = raw && hours && (!a.ids || hms_select_has(a.ids, a.nids, g));
+        uint32_t r = HMS_DROP;
+        if (!sel && !a.new_buckets.keys) r = 0;
+        if (!sel && raw && a.new_buckets.keys) {
+            r = hms_intern(a.new_buckets, bk, &bclaimed);
+            full |= r == HMS_NO_BUCKET;   /* cannot happen: no more keys than the old table held */
+        }
+        a.remap[i] = r;
+    }
+    uint64_t v[2] = {bclaimed, full};
+    hms_block_sums(v);
+    if (threadIdx.x == 0) {
+        if (v[0]) atomicAdd(&a.state[HMS_ST_BUCKETS], (unsigned long long)v[0]);
+        if (v[1]) atomicAdd(&a.state[HMS_ST_BFULL], (unsigned long long)v[1]);
+    }
+}
+
+/* Forgetting: k_stream_expire's pass (8192-cell chunks, HMS_FG_U keys in
+ * flight per thread, count, one block scan, one reservation atomic, survivors
+ * ranked by ballot row by row, the alternate arrays as target) with
+ * k_stream_select's slot map as predicate and new bucket at once: one 4-byte
+ * gather per cell, no probe, no remembered key.  The count pass leaves each
+ * thread a bit per surviving cell, so the write pass loads only survivors. */
+#define HMS_FG_U 8
+__global__ __launch_bounds__(256) void k_stream_forget(HmsForgetArgs a)
+{
+    static_assert(HMS_RL_PPT <= 32, "a thread's survivors are one 32-bit mask");
+    __shared__ uint32_t scr[256 / 64 + 1];
+    __shared__ unsigned long long sbase;
+    const int tid = threadIdx.x;
+    const uint64_t cmask = (1ull << a.cb) - 1ull;
+    constexpr uint64_t CH = 256 * HMS_RL_PPT;
+    for (uint64_t c0 = (uint64_t)blockIdx.x * CH; c0 < a.n; c0 += (uint64_t)gridDim.x * CH) {
+        uint32_t live = 0;
+        for (int j0 = 0; j0 < HMS_RL_PPT; j0 += HMS_FG_U) {
+            uint64_t k[HMS_FG_U];
+            uint32_t r[HMS_FG_U];
+#pragma unroll
+            for (int u = 0; u < HMS_FG_U; u++) {
+                const uint64_t i = c0 + (uint64_t)(j0 + u) * 256 + tid;
+                k[u] = i < a.n ? a.keys[i] : 0ull;
+            }
+#pragma unroll
+            for (int u = 0; u < HMS_FG_U; u++) {
+                const uint64_t i = c0 + (uint64_t)(j0 + u) * 256 + tid;
+                r[u] = i < a.n ? a.remap[(k[u] >> a.cb) & a.mask] : HMS_DROP;
+            }
+#pragma unroll
+            for (int u = 0; u < HMS_FG_U; u++) live |= (uint32_t)(r[u] != HMS_DROP) << (j0 + u);
+        }
+        uint32_t tot;
+        const uint32_t pos = hm_block_excl_scan<256>((uint32_t)__popc(live), scr, &tot);
+        if (tid == 0) sbase = tot ? atomicAdd(a.cursor, (unsigned long long)tot) : 0ull;
+        __syncthreads();
+        uint64_t wq = sbase + __shfl(pos, 0, 64);
+        __syncthreads();
+        if (!tot) continue;
+        for (int j0 = 0; j0 < HMS_RL_PPT; j0 += HMS_FG_U) {
+            uint64_t k[HMS_FG_U], cn[HMS_FG_U];
+            uint32_t r[HMS_FG_U];
+#pragma unroll
+            for (int u = 0; u < HMS_FG_U; u++) {
+                const uint64_t i = c0 + (uint64_t)(j0 + u) * 256 + tid;
+                const bool in = (live >> (j0 + u)) & 1u;   /* only cells below a.n are */
+                k[u] = in ? a.keys[i] : 0ull;
+                cn[u] = in ? a.counts[i] : 0ull;
+            }
+#pragma unroll
+            for (int u = 0; u < HMS_FG_U; u++) {
+                const bool in = (live >> (j0 + u)) & 1u;
+                r[u] = in ? a.remap[(k[u] >> a.cb) & a.mask] : HMS_DROP;
+            }
+#pragma unroll
+            for (int u = 0; u < HMS_FG_U; u++) {
+                const bool in = (live >> (j0 + u)) & 1u;
+                const uint64_t inb = __ballot(in);
+                if (in) {
+                    const uint64_t q = wq + hm_mbcnt(inb);
+                    a.keys_out[q] = ((uint64_t)r[u] << a.cb) | (k[u] & cmask);
+                    a.counts_out[q] = cn[u];
+                }
+                wq += (uint64_t)__popcll(inb);
+            }
+        }
+    }
+}
+
+/* The selective export's one pass (hm_stream_export_select): k_stream_export's
+ * decoding behind a ballot-ranked compaction.  A block takes 256 * HMS_XS_U
+ * cells at a time; a thread issues its keys' loads together, then the verdict
+ * gathers; the selected cells are counted (one block scan, one atomic on the
+ * cursor per chunk that holds any) and ranked row by row, and only those that
+ * land below `capacity` read their count and bucket key and are written.  The
+ * cursor counts every selected cell, so one launch gives the records and the
+ * size a larger call needs. */
+#define HMS_XS_U 8
+__global__ __launch_bounds__(256) void k_stream_export_select(HmsExportSelArgs a)
+{
+    constexpr int U = HMS_XS_U;
+    __shared__ uint32_t scr[256 / 64 + 1];
+    __shared__ unsigned long long sbase;
+    const HmsEmitArgs& e = a.e;
+    const int tid = threadIdx.x;
+    const uint64_t cmask = (1ull << e.cb) - 1ull;
+    constexpr uint64_t CH = 256 * U;
+    for (uint64_t c0 = (uint64_t)blockIdx.x * CH; c0 < e.n; c0 += (uint64_t)gridDim.x * CH) {
+        uint64_t k[U], q[U], cn[U], bk[U];
+        bool sel[U];
+        uint32_t cnt = 0;
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const uint64_t i = c0 + (uint64_t)u * 256 + tid;
+            k[u] = i < e.n ? e.keys[i] : 0ull;
+        }
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const uint64_t i = c0 + (uint64_t)u * 256 + tid;
+            sel[u] = i < e.n && a.verdict[(k[u] >> e.cb) & e.buckets.mask] == HMS_DROP;
+            cnt += sel[u];
+        }
+        uint32_t tot;
+        const uint32_t pos = hm_block_excl_scan<256>(cnt, scr, &tot);
+        if (tid == 0) sbase = tot ? atomicAdd(a.cursor, (unsigned long long)tot) : 0ull;
+        __syncthreads();
+        uint64_t wq = sbase + __shfl(pos, 0, 64);
+        __syncthreads();
+        if (!tot || wq >= a.capacity) continue;   /* (wave-uniform; no barrier below) */
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const uint64_t inb = __ballot(sel[u]);
+            q[u] = wq + hm_mbcnt(inb);
+            wq += (uint64_t)__popcll(inb);
+            sel[u] = sel[u] && q[u] < a.capacity;
+        }
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const uint64_t i = c0 + (uint64_t)u * 256 + tid;
+            cn[u] = sel[u] ? e.counts[i] : 0ull;
+            bk[u] = sel[u] ? e.buckets.keys[(k[u] >> e.cb) & e.buckets.mask] : 0ull;
+        }
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            if (!sel[u]) continue;
+            const uint32_t pw = (uint32_t)bk[u];
+            e.keys_out[q[u]] = hms_cell_key_log(k[u] & cmask, e.zmin, e.zmax);
+            e.counts_out[q[u]] = cn[u];
+            if (e.groups_out) e.groups_out[q[u]] = (uint32_t)(bk[u] >> 32);
+            if (e.periods_out) e.periods_out[q[u]] = pw == HMS_UNDATED ? HM_STREAM_UNDATED : e.base + pw;
+        }
+    }
+}
+
 /* Import of pre-aggregated cells (hm_stream_import): cell i of the input goes
  * to the log's tail at position i under the bucket of its (group, hour), so
  * the stores are as coalesced as the loads and nothing is reserved.  A block
@@ -1069,6 +1248,24 @@ void hm_launch_stream_expire(hipStream_t s, const HmsExpireArgs& a)
 {
     const uint64_t chunks = (a.n + 256 * HMS_RL_PPT - 1) / (256 * HMS_RL_PPT);
     if (a.n) hipLaunchKernelGGL(k_stream_expire, dim3((unsigned)(chunks < 1024 ? chunks : 1024)), dim3(256), 0, s, a);
+}
+
+void hm_launch_stream_select(hipStream_t s, const HmsSelectArgs& a)
+{
+    hipLaunchKernelGGL(k_stream_select, hms_grid(a.old_buckets.mask + 1), dim3(256), 0, s, a);
+}
+
+void hm_launch_stream_forget(hipStream_t s, const HmsForgetArgs& a)
+{
+    const uint64_t chunks = (a.n + 256 * HMS_RL_PPT - 1) / (256 * HMS_RL_PPT);
+    if (a.n) hipLaunchKernelGGL(k_stream_forget, dim3((unsigned)(chunks < 1024 ? chunks : 1024)), dim3(256), 0, s, a);
+}
+
+void hm_launch_stream_export_select(hipStream_t s, const HmsExportSelArgs& a)
+{
+    const uint64_t chunks = (a.e.n + 256 * HMS_XS_U - 1) / (256 * HMS_XS_U);
+    if (a.e.n)
+        hipLaunchKernelGGL(k_stream_export_select, dim3((unsigned)(chunks < 2048 ? chunks : 2048)), dim3(256), 0, s, a);
 }
 
 void hm_launch_stream_import(hipStream_t s, const HmsImportArgs& a)

@@ -20,6 +20,7 @@
 #include "hm_ctx.h"
 #include "hm_stream_frames.h"
 #include "hm_stream_rect.h"
+#include "hm_stream_select.h"
 
 namespace {
 
@@ -1000,16 +1001,18 @@ extern "C" int hm_stream_raster_frames(hm_stream* s, int64_t hour_lo, int64_t ho
     return HM_OK;
 }
 
-extern "C" int hm_stream_expire(hm_stream* s, int64_t before_hour, int64_t* cells_dropped, int64_t* buckets_freed)
+/* ---- retention and forgetting: the log filtered into the alternate arrays,
+ * the buckets that stay moved to a fresh table (hm_stream_expire,
+ * hm_stream_forget) ---- */
+
+/* Ahead of the pass: the alternate arrays and the fresh table are there (made
+ * on first use), the table is empty, and the words the pass counts into are
+ * zero: the cells kept (CURSOR), the buckets moved (BUCKETS) and, afterwards,
+ * listed (NLIST).  The stream's own bucket count comes back if nothing turns
+ * out to be dropped (stream_refile_end). */
+static int stream_refile_begin(hm_stream* s)
 {
-    if (!s) return HM_E_ARG;
-    if (cells_dropped) *cells_dropped = 0;
-    if (buckets_freed) *buckets_freed = 0;
-    const uint32_t cut = stream_hour_offset(s, before_hour);
-    if (cut == 0 || s->llen == 0) return HM_OK;   /* nothing is dated before the base hour */
-    hm_ctx* ctx = s->ctx;
-    HIPCHK(hipSetDevice(ctx->device));
-    hipStream_t q = ctx->stream;
+    hipStream_t q = s->ctx->stream;
     int st;
     premap_join(s);
     const uint64_t nb = s->bk.mask + 1;
@@ -1019,42 +1022,38 @@ extern "C" int hm_stream_expire(hm_stream* s, int64_t before_hour, int64_t* cell
         s->bk_alt = nullptr;
         return HM_E_NOMEM;
     }
-    /* the survivors' buckets are counted into BUCKETS and listed (NLIST):
-     * the stream's own count comes back if nothing turns out to expire */
-    const uint64_t old_buckets = s->nbuckets;
     unsigned long long* init = s->hstate + HMS_ST_COUNT;
     for (int j = 0; j < HMS_ST_COUNT; j++) init[j] = 0;
     /* CURSOR, BUCKETS, BFULL, EXOTIC, BMM, NLIST in one copy */
     HIPCHK(hipMemcpyAsync(s->state + HMS_ST_CURSOR, init, (HMS_ST_NLIST - HMS_ST_CURSOR + 1) * 8,
                           hipMemcpyHostToDevice, q));
     hm_launch_stream_fill(q, s->bk_alt, nb, HMS_EMPTY);
-    HmsExpireArgs a;
-    a.keys = s->log.keys.p;
-    a.counts = s->log.counts.p;
-    a.n = s->llen;
-    a.old_buckets = s->bk;
-    a.new_buckets.keys = s->bk_alt;
-    a.new_buckets.mask = s->bk.mask;
-    a.cb = s->cb;
-    a.cut = cut;
-    a.keys_out = s->alt.keys.p;
-    a.counts_out = s->alt.counts.p;
-    a.cursor = s->state + HMS_ST_CURSOR;
-    a.state = s->state;
-    hm_launch_stream_expire(q, a);
-    hm_launch_stream_occupied(q, a.new_buckets, s->blist, s->state + HMS_ST_NLIST);
+    return HM_OK;
+}
+
+/* Behind the pass: the one wait, then either nothing was dropped and the
+ * stream stays as it is (old_buckets: its bucket count before the pass), or
+ * the alternate arrays and the fresh table become the stream's. */
+static int stream_refile_end(hm_stream* s, uint64_t old_buckets, int64_t* cells_dropped, int64_t* buckets_freed)
+{
+    hipStream_t q = s->ctx->stream;
+    const uint64_t nb = s->bk.mask + 1;
+    unsigned long long* init = s->hstate + HMS_ST_COUNT;
+    hm_launch_stream_occupied(q, HmsBuckets{s->bk_alt, s->bk.mask}, s->blist, s->state + HMS_ST_NLIST);
     HIPCHK(hipGetLastError());
     /* log_buckets holds old slot ids: it is rebuilt from the new table's
-     * occupied slots, read back as a list (every one has cells in the log;
-     * there are no more of them than the old table's buckets) */
+     * occupied slots, read back as a list (a superset of the buckets with
+     * cells in the log -- a forget also carries buckets over that have none,
+     * which costs at most an early compaction; there are no more of them than
+     * the old table's buckets) */
     std::vector<uint32_t> slots((size_t)std::min<uint64_t>(old_buckets, nb));
     if (!slots.empty())
         HIPCHK(hipMemcpyAsync(slots.data(), s->blist, slots.size() * 4, hipMemcpyDeviceToHost, q));
-    st = stream_sync_state(s);
+    const int st = stream_sync_state(s);
     const uint64_t kept = s->hstate[HMS_ST_CURSOR], nslots = s->hstate[HMS_ST_NLIST];
     const bool bad = st || s->hstate[HMS_ST_BFULL] || kept > s->llen || nslots != s->nbuckets || nslots > slots.size();
     if (bad || kept == s->llen) {
-        /* nothing expired (or, cannot happen, the pass failed): the stream stays as it is */
+        /* nothing dropped (or, cannot happen, the pass failed): the stream stays as it is */
         s->nbuckets = old_buckets;
         init[0] = old_buckets;
         HIPCHK(hipMemcpyAsync(s->state + HMS_ST_BUCKETS, init, 8, hipMemcpyHostToDevice, q));
@@ -1074,6 +1073,166 @@ extern "C" int hm_stream_expire(hm_stream* s, int64_t before_hour, int64_t* cell
     HIPCHK(hipMemsetAsync(s->bflag, 0, nb * 4, q));
     s->last_nparts = 1;
     return HM_OK;
+}
+
+extern "C" int hm_stream_expire(hm_stream* s, int64_t before_hour, int64_t* cells_dropped, int64_t* buckets_freed)
+{
+    if (!s) return HM_E_ARG;
+    if (cells_dropped) *cells_dropped = 0;
+    if (buckets_freed) *buckets_freed = 0;
+    const uint32_t cut = stream_hour_offset(s, before_hour);
+    if (cut == 0 || s->llen == 0) return HM_OK;   /* nothing is dated before the base hour */
+    HIPCHK(hipSetDevice(s->ctx->device));
+    const uint64_t old_buckets = s->nbuckets;
+    int st;
+    if ((st = stream_refile_begin(s))) return st;
+    HmsExpireArgs a;
+    a.keys = s->log.keys.p;
+    a.counts = s->log.counts.p;
+    a.n = s->llen;
+    a.old_buckets = s->bk;
+    a.new_buckets.keys = s->bk_alt;
+    a.new_buckets.mask = s->bk.mask;
+    a.cb = s->cb;
+    a.cut = cut;
+    a.keys_out = s->alt.keys.p;
+    a.counts_out = s->alt.counts.p;
+    a.cursor = s->state + HMS_ST_CURSOR;
+    a.state = s->state;
+    hm_launch_stream_expire(s->ctx->stream, a);
+    return stream_refile_end(s, old_buckets, cells_dropped, buckets_freed);
+}
+
+/* ---- selections of (group, hour) buckets (hm_stream_forget,
+ * hm_stream_export_select) ---- */
+namespace {
+struct Selection {
+    std::vector<uint32_t> ids;   /* sorted and distinct; empty: every group */
+    HourWindow w;
+};
+}  // namespace
+
+/* the caller's groups and hours checked and normalised; false: HM_E_ARG */
+static bool stream_selection(const hm_stream* s, const uint32_t* groups, int64_t ngroups, int64_t hour_lo,
+                             int64_t hour_hi, Selection& sel)
+{
+    sel.w = stream_hours(s, hour_lo, hour_hi);
+    if (!s || sel.w.kind == HW_INVALID) return false;
+    if (groups ? (ngroups < 1 || ngroups > HM_SELECT_MAX_GROUPS) : ngroups != 0) return false;
+    sel.ids.resize((size_t)ngroups);
+    const int64_t m = hms_select_ids(groups, ngroups, sel.ids.data());
+    if (m < 0) return false;
+    sel.ids.resize((size_t)m);
+    return true;
+}
+
+/* The selection's verdict per bucket slot enqueued (k_stream_select), in
+ * context scratch (*map_out).  fresh: the empty table the buckets that stay
+ * are moved to (a forget), or NULL (verdicts only).  The ids' upload reads
+ * sel.ids: the caller keeps it until the stream has been waited for. */
+static int stream_select_run(hm_stream* s, const Selection& sel, uint64_t* fresh, uint32_t** map_out)
+{
+    hm_ctx* ctx = s->ctx;
+    hipStream_t q = ctx->stream;
+    uint32_t *ids = nullptr, *map = nullptr;
+    ENSURE(B_SEL_MAP, (s->bk.mask + 1) * 4, map);
+    if (!sel.ids.empty()) {
+        ENSURE(B_SEL_IDS, sel.ids.size() * 4, ids);
+        HIPCHK(hipMemcpyAsync(ids, sel.ids.data(), sel.ids.size() * 4, hipMemcpyHostToDevice, q));
+    }
+    HmsSelectArgs a;
+    a.old_buckets = s->bk;
+    a.new_buckets.keys = fresh;
+    a.new_buckets.mask = s->bk.mask;
+    a.ids = ids;
+    a.nids = (uint32_t)sel.ids.size();
+    a.alltime = sel.w.kind == HW_ALLTIME;
+    a.lo = sel.w.lo;
+    a.hi = sel.w.hi;
+    a.remap = map;
+    a.state = s->state;
+    hm_launch_stream_select(q, a);
+    HIPCHK(hipGetLastError());
+    *map_out = map;
+    return HM_OK;
+}
+
+static int stream_forget_run(hm_stream* s, const Selection& sel, int64_t* cells_dropped, int64_t* buckets_freed)
+{
+    const uint64_t old_buckets = s->nbuckets;
+    uint32_t* map = nullptr;
+    int st;
+    if ((st = stream_refile_begin(s)) || (st = stream_select_run(s, sel, s->bk_alt, &map))) return st;
+    HmsForgetArgs a;
+    a.keys = s->log.keys.p;
+    a.counts = s->log.counts.p;
+    a.n = s->llen;
+    a.remap = map;
+    a.mask = s->bk.mask;
+    a.cb = s->cb;
+    a.keys_out = s->alt.keys.p;
+    a.counts_out = s->alt.counts.p;
+    a.cursor = s->state + HMS_ST_CURSOR;
+    hm_launch_stream_forget(s->ctx->stream, a);
+    return stream_refile_end(s, old_buckets, cells_dropped, buckets_freed);
+}
+
+/* hm_stream_expire for a selection of buckets: the selected cells leave the
+ * log in one pass (k_stream_select, k_stream_forget), the buckets that stay
+ * move to a fresh table */
+extern "C" int hm_stream_forget(hm_stream* s, const uint32_t* groups, int64_t ngroups, int64_t hour_lo, int64_t hour_hi,
+                                int64_t* cells_dropped, int64_t* buckets_freed)
+{
+    Selection sel;
+    if (!stream_selection(s, groups, ngroups, hour_lo, hour_hi, sel)) return HM_E_ARG;
+    if (cells_dropped) *cells_dropped = 0;
+    if (buckets_freed) *buckets_freed = 0;
+    if (sel.w.kind == HW_EMPTY || s->llen == 0) return HM_OK;   /* no hour of the stream's, or no cell at all */
+    HIPCHK(hipSetDevice(s->ctx->device));
+    const int st = stream_forget_run(s, sel, cells_dropped, buckets_freed);
+    if (st) (void)hipStreamSynchronize(s->ctx->stream);   /* (sel.ids may still be read) */
+    return st;
+}
+
+static int stream_export_select_run(hm_stream* s, const Selection& sel, uint64_t* keys_out, uint64_t* counts_out,
+                                    uint32_t* groups_out, uint32_t* hours_out, int64_t capacity, int64_t* n_out)
+{
+    hipStream_t q = s->ctx->stream;
+    uint32_t* map = nullptr;
+    int st;
+    HIPCHK(hipMemsetAsync(s->state + HMS_ST_CURSOR, 0, 8, q));
+    if ((st = stream_select_run(s, sel, nullptr, &map))) return st;
+    HmsExportSelArgs a;
+    a.e = stream_emit_args(s, s->log.keys.p, s->log.counts.p, s->llen, keys_out, counts_out, groups_out, hours_out);
+    a.verdict = map;
+    a.capacity = (uint64_t)capacity;
+    a.cursor = s->state + HMS_ST_CURSOR;
+    hm_launch_stream_export_select(q, a);
+    HIPCHK(hipGetLastError());
+    if ((st = stream_sync_state(s))) return st;
+    *n_out = (int64_t)s->hstate[HMS_ST_CURSOR];
+    return *n_out > capacity ? HM_E_CAPACITY : HM_OK;
+}
+
+/* hm_stream_export for a selection of buckets: the compacted log's selected
+ * cells, listed and counted in one pass (k_stream_select,
+ * k_stream_export_select) */
+extern "C" int hm_stream_export_select(hm_stream* s, const uint32_t* groups, int64_t ngroups, int64_t hour_lo,
+                                       int64_t hour_hi, uint64_t* keys_out, uint64_t* counts_out, uint32_t* groups_out,
+                                       uint32_t* hours_out, int64_t capacity, int64_t* n_out)
+{
+    Selection sel;
+    if (!n_out || capacity < 0 || (capacity > 0 && (!keys_out || !counts_out)) ||
+        !stream_selection(s, groups, ngroups, hour_lo, hour_hi, sel))
+        return HM_E_ARG;
+    *n_out = 0;
+    HIPCHK(hipSetDevice(s->ctx->device));
+    int st;
+    if ((st = stream_compact(s))) return st;
+    if (sel.w.kind == HW_EMPTY || s->llen == 0) return HM_OK;
+    st = stream_export_select_run(s, sel, keys_out, counts_out, groups_out, hours_out, capacity, n_out);
+    if (st && st != HM_E_CAPACITY) (void)hipStreamSynchronize(s->ctx->stream);   /* (sel.ids may still be read) */
+    return st;
 }
 
 /* the whole log, compacted, in one pass (k_stream_export): the log's buckets

@@ -32,6 +32,12 @@ label is a device rollup of the hour buckets:
                                tile_frame_images(...) the frames on one scale
   expire(before_hour)         retention: the cells of hours < before_hour
                                leave the stream, their buckets are freed
+  forget(users, groups, hours)  erasure: the cells of these users or group
+                               ids, of these hours or of all time, leave the
+                               stream in one pass (hm_stream_forget); export(),
+                               snapshot() and merge_from() take the same three
+                               arguments and handle only that part
+                               (hm_stream_export_select)
   snapshot() / save(path)      the whole state as arrays (hm_stream_export: one
                                record per (group, hour, cell)), and back:
                                load(path), from_snapshot(), restore()
@@ -207,6 +213,85 @@ def _expire_records(x: np.ndarray, before_hour: int):
     stay."""
     h = x[:, 1]
     gone = (h != UNDATED_HOUR) & (h < before_hour)
+    return x[~gone], int(gone.sum())
+
+
+def _select_labels(users) -> list:
+    """Group labels of the reference's user ids, by the rule add(user_id=)
+    files them under (_groups): a plain id, 'all' or the literal 'route' is
+    its own label.  An 'x...' id never had a group of its own (its points sit
+    in the no-group cells, NOGROUP) and an 'rt-...' id was merged into 'route'
+    at ingest: neither can be told apart any more, so both are ValueErrors."""
+    if isinstance(users, str):
+        users = [users]
+    out = []
+    for u in users:
+        if not isinstance(u, str):
+            raise TypeError("user id %r is not a string" % (u,))
+        if u[:1] == "x":
+            raise ValueError("user id %r never had a group of its own: its points are among the cells without a "
+                             "group (groups=[NOGROUP] selects all of those)" % (u,))
+        if u[:3] == "rt-":
+            raise ValueError("user id %r was merged into 'route' when it was added: select 'route'" % (u,))
+        out.append(u)
+    return out
+
+
+def _select_ids(users, groups, index: dict):
+    """uint32 group ids of a selection: the labels of `users` that `index`
+    (label -> id) knows -- one it has never seen selects nothing and is not
+    interned -- joined with the explicit ids `groups` (0 .. NOGROUP, NOGROUP:
+    the cells without a group), in the order given, repeats kept.  None when
+    neither is given: every group."""
+    if users is None and groups is None:
+        return None
+    ids = [index[v] for v in _select_labels(users) if v in index] if users is not None else []
+    if groups is not None:
+        g = np.atleast_1d(np.asarray(groups))
+        if g.size and g.dtype.kind not in "iu":
+            raise TypeError("group ids must be integers")
+        g = g.reshape(-1).astype(np.uint64 if g.dtype.kind == "u" else np.int64)
+        bad = (g < 0) | (g > NOGROUP)
+        if bad.any():
+            raise ValueError("group id %d is outside 0 .. 0x%X" % (int(g[np.flatnonzero(bad)[0]]), NOGROUP))
+        ids += g.tolist()
+    if len(ids) > _lib.HM_SELECT_MAX_GROUPS:
+        raise ValueError("a selection takes at most %d group ids, not %d" % (_lib.HM_SELECT_MAX_GROUPS, len(ids)))
+    return np.array(ids, dtype=np.uint32)
+
+
+def _select_hours(hours):
+    """None (every hour, and the undated cells) or the pair (lo, hi) of a
+    selection's hours lo <= hour < hi, as ints"""
+    if hours is None:
+        return None
+    try:
+        lo, hi = (int(v) for v in hours)
+    except (TypeError, ValueError):
+        raise ValueError("hours must be None or a pair (lo, hi), not %r" % (hours,)) from None
+    if hi <= lo:
+        raise ValueError("hours (%d, %d) hold no hour" % (lo, hi))
+    return lo, hi
+
+
+def _select_records(x: np.ndarray, ids, hours) -> np.ndarray:
+    """Mask of the out-of-square records x (group, hour or UNDATED_HOUR, zoom,
+    row, col, count) a selection holds: group among ids (None: any) and hour
+    in hours = (lo, hi) (None: any, the undated records included; those are
+    in no range)."""
+    m = np.ones(len(x), dtype=bool)
+    if ids is not None:
+        m &= np.isin(x[:, 0], np.asarray(ids, dtype=np.int64))
+    if hours is not None:
+        h = x[:, 1]
+        m &= (h != UNDATED_HOUR) & (h >= hours[0]) & (h < hours[1])
+    return m
+
+
+def _forget_records(x: np.ndarray, ids, hours):
+    """(the records that outlive forget() of the selection, how many are
+    dropped), as _expire_records"""
+    gone = _select_records(x, ids, hours)
     return x[~gone], int(gone.sum())
 
 
@@ -842,27 +927,91 @@ class StreamingHeatmap:
         self._x, gone = _expire_records(self._x, int(before_hour))
         return a.value + gone, b.value
 
+    # ------------------------------------------------------------ selections
+
+    def _selection(self, users, groups, hours):
+        """The selection of forget / export / snapshot / merge_from checked:
+        (group ids as uint32 or None for every group, (lo, hi) or None for
+        every hour and the undated cells), or None when no argument is given.
+        users: the reference's user ids as given to add(user_id=)
+        (_select_labels); groups: explicit ids, NOGROUP for the cells without
+        a group; their union is taken."""
+        if users is None and groups is None and hours is None:
+            return None
+        return _select_ids(users, groups, self._index), _select_hours(hours)
+
+    @staticmethod
+    def _select_args(ids, hours):
+        """(groups, ngroups, hour_lo, hour_hi) of the C selection, and the
+        array the pointer reads"""
+        lo, hi = (_lib.HM_STREAM_ALLTIME, _lib.HM_STREAM_ALLTIME) if hours is None else hours
+        if ids is None:
+            return (None, 0, lo, hi), None
+        arr = np.ascontiguousarray(ids, dtype=np.uint32)
+        return (arr.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), len(arr), lo, hi), arr
+
+    def forget(self, users=None, groups=None, hours=None):
+        """Erase a part of the stream (hm_stream_forget): the cells of these
+        users (their ids as given to add(user_id=); an 'x...' or 'rt-...' id
+        is a ValueError, _select_labels) and explicit group ids (NOGROUP: the
+        cells without a group), every group when neither is given, of the
+        hours (lo, hi) or, with hours=None, of every hour and the undated
+        cells.  One pass over the log; the forgotten buckets and every rollup
+        label's are freed as expire() frees them.  Labels keep their ids, and
+        a forgotten user's label stays in `labels`.  A later add() may bring
+        the same user or hour back.  Returns (cells dropped, bucket slots
+        freed)."""
+        sel = self._selection(users, groups, hours)
+        if sel is None:
+            raise ValueError("forget() needs users, groups or hours: nothing is forgotten by default")
+        ids, hr = sel
+        self.ctx.bind_stream()
+        a, b = ctypes.c_int64(0), ctypes.c_int64(0)
+        if ids is None or len(ids):          # (no id left: none of the users is known here)
+            args, _alive = self._select_args(ids, hr)
+            rc = self.ctx.L.hm_stream_forget(self.ptr, *args, ctypes.byref(a), ctypes.byref(b))
+            _lib.raise_for(rc)
+        self._x, gone = _forget_records(self._x, ids, hr)
+        return a.value + gone, b.value
+
     # ------------------------------------------------- snapshots and merging
 
-    def export_device(self):
+    def export_device(self, users=None, groups=None, hours=None):
         """(n, keys, counts, groups, hours) as torch CUDA tensors: the whole
         resident state, one record per distinct (group, hour, cell)
         (hm_stream_export: hm_count key layout, group NOGROUP for none, hour
         HM_STREAM_UNDATED's bits for an undated cell; out-of-square cells not
-        included)."""
+        included).  With users, groups or hours (as forget()'s) only that
+        selection's records (hm_stream_export_select)."""
         self.ctx.bind_stream()
-        cap = max(1, self.cells()[0])      # exact: the export compacts the log as cells() does
-        return self._query(lambda *out: self.ctx.L.hm_stream_export(self.ptr, *out), 2, cap)
+        sel = self._selection(users, groups, hours)
+        if sel is None:
+            cap = max(1, self.cells()[0])      # exact: the export compacts the log as cells() does
+            return self._query(lambda *out: self.ctx.L.hm_stream_export(self.ptr, *out), 2, cap)
+        ids, hr = sel
+        if ids is not None and not len(ids):
+            dev = "cuda:%d" % self.device_index
+            return (0, *(self._torch.empty(0, dtype=t, device=dev)
+                         for t in (self._torch.int64,) * 2 + (self._torch.int32,) * 2))
+        args, _alive = self._select_args(ids, hr)
+        return self._query(lambda *out: self.ctx.L.hm_stream_export_select(self.ptr, *args, *out), 2,
+                           self._query_n.get("export_select", 1 << 16) + 1024, "export_select")
 
-    def export(self):
+    def _side(self, sel):
+        """the out-of-square records of a selection (None: all of them)"""
+        return self._x if sel is None else self._x[_select_records(self._x, *sel)]
+
+    def export(self, users=None, groups=None, hours=None):
         """Host arrays (group u32, hour int64, zoom, row, col, count) of every
         record held, hour UNDATED_HOUR (-1) for undated cells, cells outside
-        the square included."""
-        n, keys, counts, groups, hours = self.export_device()
-        g, h, z, r, c, cnt = self._host_cells(n, keys, counts, (groups, hours))
+        the square included; with users, groups or hours (as forget()'s) of
+        that selection only."""
+        n, keys, counts, grp, hrs = self.export_device(users, groups, hours)
+        g, h, z, r, c, cnt = self._host_cells(n, keys, counts, (grp, hrs))
         h = h.astype(np.int64)
         h[h == _lib.HM_STREAM_UNDATED] = UNDATED_HOUR
-        return self._with_side((g, h, z, r, c, cnt), self._x.T if len(self._x) else None)
+        x = self._side(self._selection(users, groups, hours))
+        return self._with_side((g, h, z, r, c, cnt), x.T if len(x) else None)
 
     def _cells_u32(self, x, n, what, undated=False):
         """uint32 values per cell as an int32 device tensor (their bits).
@@ -944,16 +1093,18 @@ class StreamingHeatmap:
         _lib.raise_for(rc)
         self._index, self.labels, self._explicit_max = index, new_labels, explicit_max
 
-    def snapshot(self) -> dict:
+    def snapshot(self, users=None, groups=None, hours=None) -> dict:
         """The stream's whole state as numpy arrays and plain numbers: format
         version, zmin, zmax, base_hour, the group labels, the largest explicit
         group id, the export (keys, counts, groups, hours as hm_stream_export
-        writes them) and the out-of-square records."""
-        n, keys, counts, groups, hours = self.export_device()
+        writes them) and the out-of-square records.  With users, groups or
+        hours (as forget()'s) the records of that selection only, under the
+        full label list, so restore() and merge_from() map it as any other."""
+        n, keys, counts, grp, hrs = self.export_device(users, groups, hours)
         return _pack_snapshot(self.zmin, self.zmax, self.base_hour, self.labels, self._explicit_max,
                               keys[:n].cpu().numpy().view(np.uint64), counts[:n].cpu().numpy().view(np.uint64),
-                              groups[:n].cpu().numpy().view(np.uint32), hours[:n].cpu().numpy().view(np.uint32),
-                              self._x)
+                              grp[:n].cpu().numpy().view(np.uint32), hrs[:n].cpu().numpy().view(np.uint32),
+                              self._side(self._selection(users, groups, hours)))
 
     def save(self, path):
         """Write snapshot() to `path` (numpy's .npz; no pickled objects)."""
@@ -1021,25 +1172,29 @@ class StreamingHeatmap:
         """A new stream from a file written by save()."""
         return cls.from_snapshot(_load_snapshot(path), **create_kwargs)
 
-    def merge_from(self, other: "StreamingHeatmap"):
+    def merge_from(self, other: "StreamingHeatmap", users=None, groups=None, hours=None):
         """Add every cell of `other` (same zooms; its base hour may differ, its
         hours must fit this stream's) to this stream: shards of one feed, or a
         backfill.  Groups are matched by label.  `other` is left unchanged;
-        nothing changes here when its hours do not fit."""
+        nothing changes here when its hours do not fit.  With users, groups or
+        hours (as forget()'s, in `other`'s ids) only that part of `other`:
+        moving users U here is merge_from(other, users=U), then
+        other.forget(users=U)."""
         torch = self._torch
         if (other.zmin, other.zmax) != (self.zmin, self.zmax):
             raise ValueError("merge_from needs equal zooms: %d..%d against %d..%d"
                              % (other.zmin, other.zmax, self.zmin, self.zmax))
-        n, keys, counts, groups, hours = other.export_device()
-        h = hours[:n].to(torch.int64) & 0xFFFFFFFF
+        n, keys, counts, grp, hrs = other.export_device(users, groups, hours)
+        ox = other._side(other._selection(users, groups, hours))
+        h = hrs[:n].to(torch.int64) & 0xFFFFFFFF
         h = h[h != _lib.HM_STREAM_UNDATED]
-        xh = other._x[other._x[:, 1] != UNDATED_HOUR, 1]
+        xh = ox[ox[:, 1] != UNDATED_HOUR, 1]
         ends = ([int(h.min()), int(h.max())] if h.numel() else []) + ([int(xh.min()), int(xh.max())] if len(xh) else [])
         self._check_hours(min(ends, default=None), max(ends, default=None), "the other stream")
         dev = "cuda:%d" % self.device_index
         self.ctx.bind_stream()
-        self._take(list(other.labels), other._explicit_max, other._x, keys[:n].to(dev), counts[:n].to(dev),
-                   groups[:n].to(dev), hours[:n].to(dev), True)
+        self._take(list(other.labels), other._explicit_max, ox, keys[:n].to(dev), counts[:n].to(dev),
+                   grp[:n].to(dev), hrs[:n].to(dev), True)
 
     def hourly(self):
         """{epoch hour: Counts} for every non-empty hour."""

@@ -305,6 +305,40 @@ int hm_last_stats(hm_ctx* ctx, int64_t* slow_points, double* stage_us, int n_sta
  *                     a cut below which the log holds nothing, changes nothing
  *                     and gives (0, 0).  A later batch may bring an expired hour
  *                     back.  Enqueued after all pending work; waits once.
+ *   A selection (hm_stream_forget, hm_stream_export_select) names raw (group,
+ *   hour) buckets.  groups: HOST uint32[ngroups], 1 <= ngroups <=
+ *   HM_SELECT_MAX_GROUPS, ids 0 .. 0xFFFFFFFE (0xFFFFFFFE: the cells without a
+ *   group) in any order, repeats allowed, ids the stream never saw select
+ *   nothing; groups == NULL with ngroups == 0: every group.  Hours [hour_lo,
+ *   hour_hi) clamped as a window's (undated cells are in no range), or the
+ *   HM_STREAM_ALLTIME pair: every hour and the undated cells.  A cell is
+ *   selected when its bucket's group is among the groups and its hour among the
+ *   hours; rollup labels hold no cells and are never selected.  HM_E_ARG, with
+ *   the stream and every output untouched and nothing enqueued: a NULL stream,
+ *   the id 0xFFFFFFFF, NULL groups with ngroups != 0, non-NULL groups with
+ *   ngroups outside 1 .. HM_SELECT_MAX_GROUPS, hour_hi <= hour_lo other than
+ *   the alltime pair.  A range wholly outside the stream's hours selects
+ *   nothing and is HM_OK.
+ *   hm_stream_forget  erasure: drops every selected cell in one pass over the
+ *                     log and moves the buckets that stay to a fresh table, as
+ *                     hm_stream_expire does: *cells_dropped and *buckets_freed
+ *                     as there (the forgotten buckets' slots and every rollup
+ *                     label's are free again; either may be NULL).  When no
+ *                     cell is dropped the stream stays exactly as it is, labels
+ *                     included, and the answer is (0, 0).  A compact log stays
+ *                     compact.  A later batch or import may bring a forgotten
+ *                     (group, hour) back.  forget(NULL, 0, base_hour,
+ *                     before_hour) drops what hm_stream_expire(before_hour)
+ *                     drops.  Enqueued after all pending work; waits once.
+ *   hm_stream_export_select  hm_stream_export restricted to the selected
+ *                     cells: the log is compacted, then one record per distinct
+ *                     selected (group, hour, cell) is written, same layouts,
+ *                     unspecified order; groups_out/hours_out may be NULL.
+ *                     *n_out: the selected records; HM_E_CAPACITY when that
+ *                     exceeds capacity (capacity 0 with NULL outputs sizes the
+ *                     call); nothing is written at or beyond capacity.  An
+ *                     empty selection is HM_OK with *n_out = 0.  The log is
+ *                     left as it is, apart from being compact.  Waits once.
  *   hm_stream_export  the stream's whole state: one record per distinct
  *                     (group, hour or undated, cell), the log compacted and
  *                     listed in one pass (no rollup).  Keys in hm_count's
@@ -369,6 +403,12 @@ int hm_stream_export(hm_stream* s, uint64_t* keys_out, uint64_t* counts_out, uin
                      uint32_t* hours_out, int64_t capacity, int64_t* n_out);
 int hm_stream_import(hm_stream* s, const uint64_t* keys, const uint64_t* counts, const uint32_t* groups,
                      const uint32_t* hours, int64_t n, int flags);
+#define HM_SELECT_MAX_GROUPS (1 << 20)
+int hm_stream_forget(hm_stream* s, const uint32_t* groups, int64_t ngroups, int64_t hour_lo, int64_t hour_hi,
+                     int64_t* cells_dropped, int64_t* buckets_freed);
+int hm_stream_export_select(hm_stream* s, const uint32_t* groups, int64_t ngroups, int64_t hour_lo, int64_t hour_hi,
+                            uint64_t* keys_out, uint64_t* counts_out, uint32_t* groups_out, uint32_t* hours_out,
+                            int64_t capacity, int64_t* n_out);
 int hm_stream_destroy(hm_stream* s);
 
 /* Rasters: what a tile server sends.  A view lists sparse (key, count) cells

@@ -86,6 +86,23 @@ written per element), next to "read_stream_GBps".  --loop-only times the two
 hm_stream_raster items alone (nothing newer is needed, so a checkout of the
 parent commit can run it); --parent-json FILE puts that run's times into this
 one's result as "parent_loop_ms" and "parent_one_raster_pass_ms".
+
+    python tools/bench_stream.py --retain 24 --batches 30 --warmup 0 --forget --out profiles/stream_forget.json
+
+--forget: the steady retained log is exported once to device arrays; every
+timed call then runs on a fresh stream that imported them and ran one expire
+that drops nothing, which makes the alternate arrays (both untimed), the calls
+taking turns within a repetition: hm_stream_expire of a cut in the middle of the
+retained hours; hm_stream_forget of the same hours (every group): the same
+cells dropped, the same bytes moved; hm_stream_forget of one middle hour, and
+the only path there was before for that (export, mask in torch, import into a
+fresh stream); hm_stream_export_select of that one hour against the full
+hm_stream_export; and, on the same cells imported with group = a hash of the
+cell % 1000, hm_stream_forget of 10 of the 1000 groups against export + mask +
+import.  Host ms around each call, which ends in its own wait; 2 warm-up
+repetitions dropped.  --expire-only times the expire alone (no newer API is
+needed, so a checkout of the parent commit can run it); --parent-json FILE puts
+that run's times into this one's result as "parent_expire_ms".
 """
 import argparse
 import json
@@ -520,6 +537,115 @@ def snapshot_bench(s, a, lat, lon, retained):
     return out
 
 
+FORGET_REPS = 7     # after 2 warm-up repetitions
+
+
+def forget_bench(s, a, lo, hi):
+    """--forget / --expire-only (module docstring) on the log of the stream as it stands"""
+    import ctypes
+
+    from heatmap_amd import _lib
+
+    L = s.ctx.L
+    n, cap = s.cells()
+    n0, keys, counts, groups, hours = s.export_device()
+    assert n0 == n
+    keys, counts, groups, hours = keys[:n], counts[:n], groups[:n], hours[:n]
+    cut, mid = lo + (hi - lo) // 2, lo + (hi - lo) // 2
+    h64 = hours.to(torch.int64) & 0xFFFFFFFF
+    below, at_mid = int((h64 < cut).sum()), int((h64 == mid).sum())
+    g1000 = ((keys ^ (keys >> 23)) * 2654435761 % 1000).to(torch.int32)     # a hash of the cell
+    ten = list(range(7, 1000, 100))
+    in_ten = int(torch.isin(g1000, torch.tensor(ten, dtype=torch.int32, device="cuda")).sum())
+    out = {"hours": [lo, hi], "log_cells": n, "log_capacity": cap, "cut": cut, "cells_below_cut": below,
+           "one_hour": mid, "cells_of_one_hour": at_mid, "cells_of_10_of_1000_groups": in_ten,
+           "repetitions": "%d after 2 warm-up ones; the calls take turns within a repetition" % FORGET_REPS,
+           "timing": "host ms around the call, which ends in its own wait; each call on a fresh stream that imported "
+                     "the exported log (untimed)"}
+    a64, b64, m64 = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+    ok = []
+
+    def fresh(grp):
+        x = StreamingHeatmap(a.zmin, a.zmax, base_hour=BASE, initial_cells=cap)
+        rc = L.hm_stream_import(x.ptr, keys.data_ptr(), counts.data_ptr(), grp.data_ptr(), hours.data_ptr(), n,
+                                _lib.HM_IMPORT_DISTINCT)
+        assert rc == 0, rc
+        # a stream in service has its alternate log arrays and table: a fresh one makes them in its first expire
+        # or forget (mapping a few GB took 0.3 - 1.7 s now and then), so one that drops nothing runs here, untimed
+        assert L.hm_stream_expire(x.ptr, BASE + 1, ctypes.byref(a64), ctypes.byref(b64)) == 0 and a64.value == 0
+        return x
+
+    def expire(x):
+        assert L.hm_stream_expire(x.ptr, cut, ctypes.byref(a64), ctypes.byref(b64)) == 0
+        ok.append(a64.value == below)
+
+    def forget(x, ids, h_lo, h_hi, want):
+        arr = (ctypes.c_uint32 * len(ids))(*ids) if ids else None
+        assert L.hm_stream_forget(x.ptr, arr, len(ids), h_lo, h_hi, ctypes.byref(a64), ctypes.byref(b64)) == 0
+        ok.append(a64.value == want)
+
+    ko, co, go, ho = (torch.empty(n, dtype=t, device="cuda") for t in (torch.int64,) * 2 + (torch.int32,) * 2)
+
+    def export_full(x):
+        rc = L.hm_stream_export(x.ptr, ko.data_ptr(), co.data_ptr(), go.data_ptr(), ho.data_ptr(), n, ctypes.byref(m64))
+        assert rc == 0 and m64.value == n, (rc, m64.value)
+
+    def export_select(x):
+        rc = L.hm_stream_export_select(x.ptr, None, 0, mid, mid + 1, ko.data_ptr(), co.data_ptr(), go.data_ptr(),
+                                       ho.data_ptr(), n, ctypes.byref(m64))
+        ok.append(rc == 0 and m64.value == at_mid)
+
+    def rebuild(x, gone):
+        """the path there was before: the whole export, a mask in torch, an import into a fresh stream"""
+        export_full(x)
+        m = ~gone(go, ho)
+        k, c, g, h = ko[m], co[m], go[m], ho[m]
+        y = StreamingHeatmap(a.zmin, a.zmax, base_hour=BASE, initial_cells=cap)
+        rc = L.hm_stream_import(y.ptr, k.data_ptr(), c.data_ptr(), g.data_ptr(), h.data_ptr(), k.numel(),
+                                _lib.HM_IMPORT_DISTINCT)
+        assert rc == 0, rc
+        rebuilt.append((y, k.numel()))
+
+    rebuilt = []
+    tens = torch.tensor(ten, dtype=torch.int32, device="cuda")
+    calls = [("expire_ms", groups, expire)]
+    if not a.expire_only:
+        calls += [
+            ("forget_same_cut_ms", groups, lambda x: forget(x, [], BASE, cut, below)),
+            ("forget_one_hour_ms", groups, lambda x: forget(x, [], mid, mid + 1, at_mid)),
+            ("rebuild_without_one_hour_ms", groups, lambda x: rebuild(x, lambda g, h: h == mid)),
+            ("export_select_one_hour_ms", groups, export_select),
+            ("export_full_ms", groups, export_full),
+            ("forget_10_of_1000_groups_ms", g1000, lambda x: forget(x, ten, -1, -1, in_ten)),
+            ("rebuild_without_10_of_1000_groups_ms", g1000, lambda x: rebuild(x, lambda g, h: torch.isin(g, tens))),
+        ]
+    t = {name: [] for name, _, _ in calls}
+    for rep in range(FORGET_REPS + 2):
+        for name, grp, call in calls:
+            x = fresh(grp)
+            t[name].append(_ms(lambda: call(x))[0])
+            x.close()
+            while rebuilt:
+                y, left = rebuilt.pop()
+                ok.append(y.cells()[0] == left)
+                y.close()
+        print("forget rep %d: %s" % (rep, ", ".join("%s %.2f" % (k, v[-1]) for k, v in t.items())), file=sys.stderr,
+              flush=True)
+    for name in t:
+        out[name] = _stats(t[name][2:])
+        out[name]["all"] = t[name][2:]
+    out["check"] = "ok" if all(ok) else "FAIL"
+    out["bytes"] = ("expire and forget of the cut: 16 B per log cell read + 16 B per survivor written; export: 16 B "
+                    "read + 24 B written per record")
+    if a.parent_json:
+        pj = json.load(open(a.parent_json))["forget"]
+        assert pj["log_cells"] == n and pj["check"] == "ok" and pj["cut"] == cut
+        out["parent_expire_ms"] = pj["expire_ms"]
+        out["parent_note"] = ("this script with --forget --expire-only run by a checkout of the parent commit (its "
+                              "library and package) on the same seeded log, in the same session")
+    return out
+
+
 def retain(a):
     """--retain H: a stream under retention (module docstring)"""
     n, H = int(a.batch), a.retain
@@ -552,6 +678,7 @@ def retain(a):
     snap = snapshot_bench(s, a, lat, lon, list(range(total - 1 - H, total))) if a.snapshot or a.readd_only else None
     ras = raster_bench(s, a, BASE + total - 1 - H, BASE + total) if a.raster else None
     fra = frames_bench(s, a, BASE + total) if a.frames else None
+    fgt = forget_bench(s, a, BASE + total - 1 - H, BASE + total) if a.forget or a.expire_only else None
     result = json.dumps({
         "metric": "stream under retention: expire(newest - H) and window(newest - H, newest + 1) per one-hour batch",
         "retain_hours": H, "batch_points": n, "batches": a.batches, "warmup": a.warmup, "zooms": [a.zmin, a.zmax],
@@ -568,6 +695,7 @@ def retain(a):
         "snapshot": snap,
         "raster": ras,
         "frames": fra,
+        "forget": fgt,
         "series": series,
         "data": "synthetic (heatmap_amd.synth, generated on device, resident in HBM)"})
     print(result)
@@ -603,13 +731,17 @@ def main():
                     help="with --retain 24 or more: 24 hourly frames of a screen in one call vs one raster call per "
                          "hour (module docstring)")
     ap.add_argument("--loop-only", action="store_true", help="with --frames: time the per-hour raster calls alone")
+    ap.add_argument("--forget", action="store_true",
+                    help="with --retain: forget and selective export on the steady log against expire, the full "
+                         "export and export + mask + import (module docstring)")
+    ap.add_argument("--expire-only", action="store_true", help="with --retain: --forget's expire alone")
     ap.add_argument("--readd-only", action="store_true",
                     help="with --retain: time only the re-adding of the retained batches to a fresh stream")
     ap.add_argument("--parent-json", default=None, metavar="FILE",
                     help="with --view: a --window-only result of the parent commit, kept as parent_window; with "
                          "--snapshot: its --readd-only result, kept as parent_readd_ms; with --raster: its "
                          "--view-only result, kept as parent_view_ms; with --frames: its --loop-only result, kept as "
-                         "parent_loop_ms")
+                         "parent_loop_ms; with --forget: its --expire-only result, kept as parent_expire_ms")
     ap.add_argument("--out", default=None, metavar="FILE", help="with --retain: also write the JSON line to FILE")
     a = ap.parse_args()
     if a.retain > 0:
