@@ -19,7 +19,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "_lib")
 LIB = os.path.join(LIBDIR, "libheatmap_amd.so")
 SOURCES = ["hm_kernels.hip", "hm_aggregate.hip", "hm_general.hip", "hm_stream.hip", "hm_merge.hip", "hm_raster.hip",
-           "hm_api.cpp", "hm_stream_api.cpp", "hm_host.c"]
+           "hm_top.hip", "hm_api.cpp", "hm_stream_api.cpp", "hm_host.c"]
 ARCH = os.environ.get("HM_OFFLOAD_ARCH", "gfx950")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "--offload-arch=" + ARCH,
          "-Wall", "-Wno-unused-function", "-Wno-unused-variable", "-Wno-unknown-pragmas",

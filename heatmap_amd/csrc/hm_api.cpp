@@ -2328,6 +2328,61 @@ extern "C" int hm_bench_read(hm_ctx* ctx, const void* a, const void* b, int64_t 
     return HM_OK;
 }
 
+/* ---- top-k selection (hm_top.hip) ---- */
+
+int cells_top(hm_ctx* ctx, const uint64_t* keys, const uint64_t* counts, int64_t n, int64_t k, uint64_t* keys_out,
+              uint64_t* counts_out)
+{
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t q = ctx->stream;
+    if (n <= k) {   /* every record: only the order is missing */
+        hm_launch_top_sort(q, keys, counts, (uint64_t)n, nullptr, keys_out, counts_out);
+        HIPCHK(hipGetLastError());
+        return HM_OK;
+    }
+    unsigned char* scratch;
+    HmTopArgs a;
+    ENSURE(B_TOP_SCRATCH, HM_TOP_SCRATCH_BYTES, scratch);
+    ENSURE(B_TOP_KEYS, HM_TOP_MAX_K * 8, a.sel_keys);
+    ENSURE(B_TOP_COUNTS, HM_TOP_MAX_K * 8, a.sel_counts);
+    HIPCHK(hipMemsetAsync(scratch, 0, HM_TOP_SCRATCH_BYTES, q));
+    a.keys = keys;
+    a.counts = counts;
+    a.n = (uint64_t)n;
+    a.k = (uint64_t)k;
+    a.words = (unsigned long long*)scratch;
+    a.states = (HmTopState*)(scratch + HM_TOP_W_COUNT * 8);
+    a.hist = (unsigned long long*)(scratch + HM_TOP_W_COUNT * 8 + (HM_TOP_PASSES + 1) * sizeof(HmTopState));
+    hm_launch_top_select(q, a);
+    hm_launch_top_sort(q, a.sel_keys, a.sel_counts, (uint64_t)k, a.words + HM_TOP_W_CURSOR, keys_out, counts_out);
+    HIPCHK(hipGetLastError());
+    return HM_OK;
+}
+
+/* do the byte ranges [a, a + na) and [b, b + nb) share a byte */
+static bool ranges_overlap(const void* a, uint64_t na, const void* b, uint64_t nb)
+{
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + nb && y < x + na;
+}
+
+extern "C" int hm_cells_top(hm_ctx* ctx, const uint64_t* keys, const uint64_t* counts, int64_t n, int64_t k,
+                            uint64_t* keys_out, uint64_t* counts_out, int64_t* n_out)
+{
+    if (!ctx || !n_out || n < 0 || k < 1 || k > HM_TOP_MAX_K || (n > 0 && (!keys || !counts || !keys_out || !counts_out)))
+        return HM_E_ARG;
+    if (n > 0) {
+        const uint64_t in = (uint64_t)n * 8, out = (uint64_t)k * 8;
+        for (const void* o : {(const void*)keys_out, (const void*)counts_out})
+            if (ranges_overlap(o, out, keys, in) || ranges_overlap(o, out, counts, in)) return HM_E_ARG;
+        if (ranges_overlap(keys_out, out, counts_out, out)) return HM_E_ARG;
+    }
+    /* written once the work is enqueued (no wait), so that a failure leaves it as it was */
+    const int st = n ? cells_top(ctx, keys, counts, n, k, keys_out, counts_out) : HM_OK;
+    if (st == HM_OK) *n_out = n < k ? n : k;
+    return st;
+}
+
 /* ---- rasters: dense tile grids and rendered tiles (hm_raster.hip) ---- */
 
 /* the shared argument check of the two scatters: tiles inside their squares,

@@ -101,6 +101,7 @@ enum {
     B_L1_SLOT,
     B_RS_B, B_RS_MX,   /* hm_raster_render: blurred counts, the two maxima */
     B_SEL_IDS, B_SEL_MAP,   /* a stream selection: the sorted group ids, the word per bucket slot */
+    B_TOP_SCRATCH, B_TOP_KEYS, B_TOP_COUNTS,   /* cells_top: words, states and histograms; the collected records */
     B_COUNT
 };
 
@@ -138,6 +139,11 @@ HM_INTERNAL int grouped_impl(hm_ctx* ctx, const double* lat, const double* lon, 
 HM_INTERNAL int cells_merge(hm_ctx* ctx, const void* keys_in, const void* counts_in, int layout, int64_t n,
                             const int64_t* runs, int nruns, uint64_t* keys_out, uint64_t* counts_out, int64_t capacity,
                             int64_t* n_out);
+/* the first min(n, k) of n device records in rank order (hm_cells_top without
+ * its argument checks: n > 0, 1 <= k <= HM_TOP_MAX_K, outputs of min(n, k)
+ * entries that do not overlap the inputs); asynchronous, no read-back */
+HM_INTERNAL int cells_top(hm_ctx* ctx, const uint64_t* keys, const uint64_t* counts, int64_t n, int64_t k,
+                          uint64_t* keys_out, uint64_t* counts_out);
 HM_INTERNAL bool raster_args_ok(const int64_t* tiles, int ntiles, int bins_log2, int halo, int zlo, int zhi);
 
 #endif

@@ -46,6 +46,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "hm_top_select.h"
+
 /* level 1: projection + partition by the zoom-z1 digit */
 #ifndef HM_P1_THREADS
 #define HM_P1_THREADS 512
@@ -846,9 +848,52 @@ void hm_launch_stream_emit(hipStream_t s, const HmsEmitArgs& a);
 /* the log itself -> caller's arrays: periods_out receives epoch hours or HM_STREAM_UNDATED (k_stream_export) */
 void hm_launch_stream_export(hipStream_t s, const HmsEmitArgs& a);
 void hm_launch_stream_view(hipStream_t s, const HmsViewArgs& a);
+/* the same filter with every survivor keyed by its group id alone, the equal
+ * groups of a wave row summed before they are written (k_stream_view_groups;
+ * gmode is not read: every group passes) */
+void hm_launch_stream_view_groups(hipStream_t s, const HmsViewArgs& a);
 void hm_launch_stream_expire(hipStream_t s, const HmsExpireArgs& a);
 /* the occupied slots of a bucket table -> list, their number added to *n */
 void hm_launch_stream_occupied(hipStream_t s, const HmsBuckets& b, uint32_t* list, unsigned long long* n);
+
+/* top-k selection of (key, count) records (hm_top.hip; the digit walk is
+ * hm_top_select.h).  One scratch block holds everything the passes hand each
+ * other on the device: the words, the state each launch leaves for the next,
+ * one global histogram per pass. */
+#define HM_TOP_THREADS 256
+#define HM_TOP_SORT_THREADS 1024
+#define HM_TOP_PASSES 16                 /* launches of k_top_pass: 8 count digits + 8 key digits at most */
+enum {
+    HM_TOP_W_ORC = 0, HM_TOP_W_NANDC = 1 /* OR of ~count: the AND, from zeroed words */, HM_TOP_W_ORK = 2,
+    HM_TOP_W_NANDK = 3, HM_TOP_W_CURSOR = 4 /* records collected */,
+    HM_TOP_W_LAST = 5 /* records met at the last (count, key) taken */, HM_TOP_W_COUNT = 8
+};
+enum { HM_TOP_COUNTS = 0, HM_TOP_KEYS = 1, HM_TOP_DONE = 2 };
+struct HmTopState {
+    HmTopWalk c;             /* over the counts, descending: prefix -> the k-th largest count T, beyond -> records above T */
+    HmTopWalk k;             /* over the keys of the records at T, ascending: prefix -> the last key taken (~0: all) */
+    uint32_t phase, pad;
+};
+#define HM_TOP_SCRATCH_BYTES \
+    (HM_TOP_W_COUNT * 8 + (HM_TOP_PASSES + 1) * sizeof(HmTopState) + (size_t)HM_TOP_PASSES * HM_TOP_BINS * 8)
+struct HmTopArgs {
+    const uint64_t* keys;
+    const uint64_t* counts;
+    uint64_t n, k;           /* n > k >= 1 */
+    unsigned long long* words;   /* [HM_TOP_W_COUNT], zeroed */
+    HmTopState* states;      /* [HM_TOP_PASSES + 1] */
+    unsigned long long* hist;    /* [HM_TOP_PASSES][HM_TOP_BINS], zeroed */
+    uint64_t* sel_keys;      /* [k] the collected records, unordered */
+    uint64_t* sel_counts;
+};
+/* reduce, the passes and the collect: words[HM_TOP_W_CURSOR] records (k of them
+ * over distinct keys) in sel_keys / sel_counts */
+void hm_launch_top_select(hipStream_t s, const HmTopArgs& a);
+/* the first min(m, *m_dev when given, HM_TOP_MAX_K) records into rank order */
+void hm_launch_top_sort(hipStream_t s, const uint64_t* keys, const uint64_t* counts, uint64_t m,
+                        const unsigned long long* m_dev, uint64_t* keys_out, uint64_t* counts_out);
+void hm_launch_top_narrow(hipStream_t s, const uint64_t* keys, const uint64_t* counts, uint64_t m, uint32_t* ids_out,
+                          uint64_t* counts_out);
 
 /* general count path (hm_general.hip): sort of 128-bit cell keys + zoom cascade */
 struct HmGenArgs {

@@ -33,6 +33,10 @@
  * into dense per-tile grids: equal cells meet in one bin, so nothing is merged.
  * Frames (hm_stream_raster_frames, k_stream_raster_frames) are the same pass
  * with each survivor sent to the grids of its own hour's frame.
+ * A ranking (hm_stream_top) is a view whose merged cells go through the top-k
+ * selection (hm_top.hip) before the emit, so k cells leave, not all of them;
+ * a ranking of groups (hm_stream_top_groups) keys the survivors by group alone
+ * (k_stream_view_groups) before the same merge and selection.
  * Retention (hm_stream_expire, k_stream_expire)
  * filters the log into the alternate arrays and moves the surviving buckets
  * to a fresh bucket table, which frees the slots of the expired hours and of
@@ -630,6 +634,141 @@ __global__ __launch_bounds__(256) void k_stream_view(HmsViewArgs a)
         if (v[1]) atomicAdd(&a.state[HMS_ST_BFULL], (unsigned long long)v[1]);
     }
 }
+
+/* A ranking of groups (hm_stream_top_groups): k_stream_view's filter -- the
+ * same interval, rectangle and hour tests -- with every survivor keyed by its
+ * group id alone (no label is interned, gmode is not read).  Survivors are many
+ * and groups few, and the merge that follows takes a bucket of equal keys in
+ * passes over all of it, so equal groups are summed before anything is
+ * written: a wave row's survivors of one group across the wave (the first
+ * HMS_VG_TURNS groups of a row; the others go on as they are), then those sums
+ * in a table of the block's in LDS, written once when the block ends.  A sum
+ * that finds no slot within HMS_VG_PROBES is written as a record of its own,
+ * with one reservation per wave and chunk as k_stream_view's.  The merge sees
+ * at most a record per (block, group) and those few. */
+#define HMS_VG_TURNS 4
+#define HMS_VG_SLOTS 2048
+#define HMS_VG_PROBES 16
+__global__ __launch_bounds__(256) void k_stream_view_groups(HmsViewArgs a)
+{
+    constexpr int U = HMS_VW_U;
+    __shared__ uint32_t tg[HMS_VG_SLOTS];             /* group ids, HMS_ALLGROUPS: empty (no cell has that group) */
+    __shared__ unsigned long long ts[HMS_VG_SLOTS];
+    __shared__ uint32_t scr[256 / 64 + 1];
+    __shared__ unsigned long long sbase;
+    const int tid = threadIdx.x;
+    const uint32_t lane = (uint32_t)tid & 63u;
+    const uint64_t cmask = (1ull << a.cb) - 1ull;
+    constexpr uint64_t CH = 256 * U;
+    for (int j = tid; j < HMS_VG_SLOTS; j += 256) {
+        tg[j] = HMS_ALLGROUPS;
+        ts[j] = 0;
+    }
+    __syncthreads();
+    for (uint64_t c0 = (uint64_t)blockIdx.x * CH; c0 < a.n; c0 += (uint64_t)gridDim.x * CH) {
+        uint64_t k[U];
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const uint64_t i = c0 + (uint64_t)u * 256 + tid;
+            k[u] = i < a.n ? a.keys[i] : 0ull;
+        }
+        uint32_t box = 0;
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const uint64_t i = c0 + (uint64_t)u * 256 + tid;
+            box |= (uint32_t)(i < a.n && (k[u] & cmask) - a.box_lo < a.box_span) << u;
+        }
+        if (!__ballot(box != 0)) continue;
+        uint32_t hit = 0;
+        for (int r = 0; r < a.nrects; r++) {
+            const HmsViewRect R = a.rects[r];
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+                const uint64_t d = (k[u] & cmask) - R.id_lo;
+                hit |= (uint32_t)(d < R.span && ((uint32_t)d & R.cmask) - R.col_lo < R.col_w) << u;
+            }
+        }
+        hit &= box;
+        if (!__ballot(hit != 0)) continue;
+        uint32_t g[U];
+        uint64_t sum[U], heads[U];    /* a group's first lane of the row holds its sum; heads: those lanes not in the table */
+        uint32_t tot = 0;
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const uint64_t i = c0 + (uint64_t)u * 256 + tid;
+            bool in = (hit >> u) & 1u;
+            g[u] = 0;
+            if (in) {
+                const uint64_t bk = a.buckets.keys[(k[u] >> a.cb) & a.buckets.mask];
+                const uint32_t pw = (uint32_t)bk;
+                const bool dated = (pw >> 28) == 0;
+                in = a.alltime ? (dated || pw == HMS_UNDATED) : (dated && pw >= a.lo && pw < a.hi);
+                g[u] = (uint32_t)(bk >> 32);
+            }
+            const uint64_t cn = in ? a.counts[i] : 0ull;
+            uint64_t left = __ballot(in);
+            sum[u] = 0, heads[u] = 0;
+            for (int turn = 0; left; turn++) {   /* one turn per distinct group of the row */
+                if (turn == HMS_VG_TURNS) {      /* many groups: the rest go out as they are */
+                    if ((left >> lane) & 1ull) sum[u] = cn;
+                    heads[u] |= left;
+                    break;
+                }
+                const int leader = __ffsll((unsigned long long)left) - 1;
+                const uint32_t g0 = __shfl(g[u], leader, 64);
+                const bool mine = in && g[u] == g0;
+                uint64_t t = mine ? cn : 0ull;
+#pragma unroll
+                for (int d = 32; d >= 1; d >>= 1) t += __shfl_xor((unsigned long long)t, d, 64);
+                if ((int)lane == leader) sum[u] = t;
+                heads[u] |= 1ull << leader;
+                left &= ~__ballot(mine);
+            }
+            bool placed = false;
+            if ((heads[u] >> lane) & 1ull) {
+                uint32_t sl = (uint32_t)hms_hash(g[u]) & (HMS_VG_SLOTS - 1);
+                for (int probe = 0; probe < HMS_VG_PROBES && !placed; probe++) {
+                    const uint32_t o = atomicCAS(&tg[sl], HMS_ALLGROUPS, g[u]);
+                    placed = o == HMS_ALLGROUPS || o == g[u];
+                    if (placed) atomicAdd(&ts[sl], (unsigned long long)sum[u]);
+                    sl = (sl + 1) & (HMS_VG_SLOTS - 1);
+                }
+            }
+            heads[u] &= ~__ballot(placed);
+            tot += (uint32_t)__popcll(heads[u]);
+        }
+        if (!tot) continue;
+        unsigned long long first = 0;
+        if (lane == 0) first = atomicAdd(a.cursor, (unsigned long long)tot);
+        uint64_t wq = __shfl(first, 0, 64);
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            if ((heads[u] >> lane) & 1ull) {
+                const uint64_t q = wq + hm_mbcnt(heads[u]);
+                a.keys_out[q] = g[u];
+                a.counts_out[q] = sum[u];
+            }
+            wq += (uint64_t)__popcll(heads[u]);
+        }
+    }
+    /* the block's table: its sums out, one reservation */
+    __syncthreads();
+    constexpr int SPT = HMS_VG_SLOTS / 256;
+    uint32_t c = 0;
+    for (int j = 0; j < SPT; j++) c += tg[tid * SPT + j] != HMS_ALLGROUPS;
+    uint32_t total;
+    uint32_t off = hm_block_excl_scan<256>(c, scr, &total);
+    const unsigned long long base = hm_block_reserve(a.cursor, total, &sbase);
+    for (int j = 0; j < SPT; j++) {
+        const uint32_t sl = tid * SPT + j;
+        if (tg[sl] != HMS_ALLGROUPS) {
+            a.keys_out[base + off] = tg[sl];
+            a.counts_out[base + off] = ts[sl];
+            off++;
+        }
+    }
+}
+
 
 /* is a raw bucket key inside a raster's hours and group */
 __device__ __forceinline__ bool hms_raster_in(const HmsRasterArgs& a, uint64_t bk)
@@ -1229,6 +1368,13 @@ void hm_launch_stream_view(hipStream_t s, const HmsViewArgs& a)
 {
     const uint64_t chunks = (a.n + 256 * HMS_VW_U - 1) / (256 * HMS_VW_U);
     if (a.n) hipLaunchKernelGGL(k_stream_view, dim3((unsigned)(chunks < 2048 ? chunks : 2048)), dim3(256), 0, s, a);
+}
+
+void hm_launch_stream_view_groups(hipStream_t s, const HmsViewArgs& a)
+{
+    const uint64_t chunks = (a.n + 256 * HMS_VW_U - 1) / (256 * HMS_VW_U);
+    if (a.n)
+        hipLaunchKernelGGL(k_stream_view_groups, dim3((unsigned)(chunks < 2048 ? chunks : 2048)), dim3(256), 0, s, a);
 }
 
 void hm_launch_stream_raster(hipStream_t s, const HmsRasterArgs& a)

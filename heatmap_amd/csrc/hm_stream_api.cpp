@@ -84,6 +84,7 @@ struct hm_stream {
     Buf plat, plon, pkeep, pstart;        /* partition path: bucket-contiguous batch */
     int64_t rcap = 0;                     /* records rec holds */
     Buf rk, rc, mk, mc;                   /* rollup scratch: relabeled and merged cells */
+    Buf tk, tc;                           /* a ranking's HM_TOP_MAX_K records (hm_stream_top*) */
     /* several-bucket batches: up to HMS_PAR buckets counted at once, each by
      * its own context, stream and host thread, into its own scratch */
     hm_ctx* pctx[HMS_PAR] = {};
@@ -785,23 +786,29 @@ static int stream_filter_begin(hm_stream* s, Args& a, bool* empty)
     return HM_OK;
 }
 
-/* the tail of every such query: the filter pass's read-back, then the label
- * cells in the scratch arrays (HMS_ST_CURSOR of them) merged and emitted */
+/* the filter pass's read-back, then the cells it left in the scratch arrays
+ * (HMS_ST_CURSOR of them) with equal keys summed: *nd distinct cells in mk / mc */
+static int stream_merge(hm_stream* s, int64_t* nd)
+{
+    int st;
+    *nd = 0;
+    if ((st = stream_sync_state(s))) return st;
+    if (s->hstate[HMS_ST_BFULL]) return HM_E_CAPACITY;   /* no bucket left for a rollup label */
+    const uint64_t m = s->hstate[HMS_ST_CURSOR];
+    if (m == 0) return HM_OK;
+    if ((st = stream_buf(s->mk, m * 8)) || (st = stream_buf(s->mc, m * 8))) return st;
+    return cells_merge(s->ctx, (const uint64_t*)s->rk.p, (const uint64_t*)s->rc.p, HM_CELLS_U64, (int64_t)m, nullptr, 0,
+                       (uint64_t*)s->mk.p, (uint64_t*)s->mc.p, (int64_t)m, nd);
+}
+
+/* the tail of every such query: the label cells merged and emitted */
 static int stream_merge_emit(hm_stream* s, uint64_t* keys_out, uint64_t* counts_out, uint32_t* groups_out,
                              uint32_t* periods_out, int64_t capacity, int64_t* n_out)
 {
     hm_ctx* ctx = s->ctx;
     int st;
-    if ((st = stream_sync_state(s))) return st;
-    if (s->hstate[HMS_ST_BFULL]) return HM_E_CAPACITY;   /* no bucket left for a rollup label */
-    const uint64_t m = s->hstate[HMS_ST_CURSOR];
-    if (m == 0) return HM_OK;
-    /* equal label cells summed */
-    if ((st = stream_buf(s->mk, m * 8)) || (st = stream_buf(s->mc, m * 8))) return st;
     int64_t nd = 0;
-    if ((st = cells_merge(ctx, (const uint64_t*)s->rk.p, (const uint64_t*)s->rc.p, HM_CELLS_U64, (int64_t)m, nullptr, 0,
-                          (uint64_t*)s->mk.p, (uint64_t*)s->mc.p, (int64_t)m, &nd)))
-        return st;
+    if ((st = stream_merge(s, &nd)) || nd == 0) return st;
     *n_out = nd;
     if (nd > capacity) return HM_E_CAPACITY;
     hm_launch_stream_emit(ctx->stream, stream_emit_args(s, (const uint64_t*)s->mk.p, (const uint64_t*)s->mc.p,
@@ -874,16 +881,21 @@ extern "C" int hm_stream_window(hm_stream* s, int64_t hour_lo, int64_t hour_hi, 
                          capacity, n_out);
 }
 
-extern "C" int hm_stream_view(hm_stream* s, int64_t hour_lo, int64_t hour_hi, int64_t group, const int64_t* rects,
-                              int nrects, uint64_t* keys_out, uint64_t* counts_out, uint32_t* groups_out,
-                              int64_t capacity, int64_t* n_out)
+/* A view's filter pass (hm_stream_view, hm_stream_top, hm_stream_top_groups):
+ * the rectangles, hours and group checked and the log's cells of the selection
+ * written to the scratch arrays, re-keyed to the view's label -- or, by_group,
+ * keyed by their group id alone.  *empty: nothing can be selected, no pass ran.
+ * one_zoom: rectangles of different zooms are refused.  n_out: hm_stream_view's,
+ * zeroed once the arguments checked before the rectangles have passed. */
+static int stream_view_filter(hm_stream* s, int64_t hour_lo, int64_t hour_hi, int64_t group, const int64_t* rects,
+                              int nrects, bool by_group, bool one_zoom, bool* empty, int64_t* n_out = nullptr)
 {
     const HourWindow w = stream_hours(s, hour_lo, hour_hi);
-    if (!s || !n_out || !rects || nrects < 1 || nrects > HM_VIEW_MAX_RECTS || w.kind == HW_INVALID ||
-        group < HM_VIEW_EACH || group > (int64_t)HMS_NOGROUP || capacity < 0 ||
-        (capacity > 0 && (!keys_out || !counts_out)))
+    *empty = true;
+    if (!s || !rects || nrects < 1 || nrects > HM_VIEW_MAX_RECTS || w.kind == HW_INVALID || group < HM_VIEW_EACH ||
+        group > (int64_t)HMS_NOGROUP)
         return HM_E_ARG;
-    *n_out = 0;
+    if (n_out) *n_out = 0;   /* hm_stream_view: zero from here on, also when a rectangle is refused below */
     HmsViewArgs a;
     a.nrects = 0;
     uint64_t box_hi = 0;
@@ -891,7 +903,7 @@ extern "C" int hm_stream_view(hm_stream* s, int64_t hour_lo, int64_t hour_hi, in
     for (int r = 0; r < nrects; r++) {
         const int64_t z = rects[5 * r], side = 1ll << (z < 0 || z > HM_MAX_ZOOM ? 0 : z);
         int64_t rlo = rects[5 * r + 1], rhi = rects[5 * r + 2], clo = rects[5 * r + 3], chi = rects[5 * r + 4];
-        if (z < s->zmin || z > s->zmax || rhi <= rlo || chi <= clo) return HM_E_ARG;
+        if (z < s->zmin || z > s->zmax || rhi <= rlo || chi <= clo || (one_zoom && z != rects[0])) return HM_E_ARG;
         /* clipped to the square; what is left may be nothing */
         rlo = std::max<int64_t>(rlo, 0), clo = std::max<int64_t>(clo, 0);
         rhi = std::min<int64_t>(rhi, side), chi = std::min<int64_t>(chi, side);
@@ -906,15 +918,92 @@ extern "C" int hm_stream_view(hm_stream* s, int64_t hour_lo, int64_t hour_hi, in
     a.lo = w.lo, a.hi = w.hi;
     a.gmode = group == HM_VIEW_MERGED ? HMS_VIEW_MERGED : (group == HM_VIEW_EACH ? HMS_VIEW_EACH : HMS_VIEW_GROUP);
     a.group = group >= 0 ? (uint32_t)group : 0u;
+    HIPCHK(hipSetDevice(s->ctx->device));
+    const int st = stream_filter_begin(s, a, empty);
+    if (st || *empty) return st;
+    if (by_group)
+        hm_launch_stream_view_groups(s->ctx->stream, a);
+    else
+        hm_launch_stream_view(s->ctx->stream, a);
+    HIPCHK(hipGetLastError());
+    return HM_OK;
+}
+
+extern "C" int hm_stream_view(hm_stream* s, int64_t hour_lo, int64_t hour_hi, int64_t group, const int64_t* rects,
+                              int nrects, uint64_t* keys_out, uint64_t* counts_out, uint32_t* groups_out,
+                              int64_t capacity, int64_t* n_out)
+{
+    if (!n_out || capacity < 0 || (capacity > 0 && (!keys_out || !counts_out))) return HM_E_ARG;
     /* a view's three passes: filter (k_stream_view, in place of the relabel),
      * then the rollup's merge and emit over the survivors only */
-    HIPCHK(hipSetDevice(s->ctx->device));
     bool empty;
-    const int st = stream_filter_begin(s, a, &empty);
+    const int st = stream_view_filter(s, hour_lo, hour_hi, group, rects, nrects, false, false, &empty, n_out);
     if (st || empty) return st;
-    hm_launch_stream_view(s->ctx->stream, a);
-    HIPCHK(hipGetLastError());
     return stream_merge_emit(s, keys_out, counts_out, groups_out, nullptr, capacity, n_out);
+}
+
+/* the selection over a query's merged cells (mk / mc, nd of them) into the
+ * stream's ranked scratch: min(nd, k) records in rank order in tk / tc */
+static int stream_rank(hm_stream* s, int64_t nd, int64_t k)
+{
+    int st;
+    if ((st = stream_buf(s->tk, HM_TOP_MAX_K * 8)) || (st = stream_buf(s->tc, HM_TOP_MAX_K * 8))) return st;
+    return cells_top(s->ctx, (const uint64_t*)s->mk.p, (const uint64_t*)s->mc.p, nd, k, (uint64_t*)s->tk.p,
+                     (uint64_t*)s->tc.p);
+}
+
+extern "C" int hm_stream_top(hm_stream* s, int64_t hour_lo, int64_t hour_hi, int64_t group, const int64_t* rects,
+                             int nrects, int64_t k, uint64_t* keys_out, uint64_t* counts_out, int64_t* n_out,
+                             int64_t* cells_out)
+{
+    if (!n_out || !keys_out || !counts_out || k < 1 || k > HM_TOP_MAX_K || group == HM_VIEW_EACH) return HM_E_ARG;
+    /* the view's filter and merge, then the selection, then the view's emit
+     * of the chosen records only */
+    bool empty;
+    int st = stream_view_filter(s, hour_lo, hour_hi, group, rects, nrects, false, false, &empty);
+    if (st == HM_E_ARG) return st;
+    *n_out = 0;
+    if (cells_out) *cells_out = 0;
+    if (st || empty) return st;
+    int64_t nd = 0;
+    if ((st = stream_merge(s, &nd)) || nd == 0) return st;
+    /* One label is in play (merged, or one group), so every merged key has
+     * the same bucket bits, and the cell bits -- the pyramid id, ordered by
+     * zoom, then row, then column -- order as HM_KEY does: ranking the
+     * internal keys is ranking the emitted ones. */
+    if ((st = stream_rank(s, nd, k))) return st;
+    const int64_t m = std::min(nd, k);
+    hm_launch_stream_emit(s->ctx->stream, stream_emit_args(s, (const uint64_t*)s->tk.p, (const uint64_t*)s->tc.p,
+                                                           (uint64_t)m, keys_out, counts_out, nullptr, nullptr));
+    HIPCHK(hipGetLastError());
+    *n_out = m;
+    if (cells_out) *cells_out = nd;
+    return HM_OK;
+}
+
+extern "C" int hm_stream_top_groups(hm_stream* s, int64_t hour_lo, int64_t hour_hi, const int64_t* rects, int nrects,
+                                    int64_t k, uint32_t* groups_out, uint64_t* counts_out, int64_t* n_out,
+                                    int64_t* groups_total_out)
+{
+    if (!n_out || !groups_out || !counts_out || k < 1 || k > HM_TOP_MAX_K) return HM_E_ARG;
+    /* the survivors keyed by group alone (k_stream_view_groups), then the same
+     * merge and selection; the keys are the group ids themselves */
+    bool empty;
+    int st = stream_view_filter(s, hour_lo, hour_hi, HM_VIEW_MERGED, rects, nrects, true, true, &empty);
+    if (st == HM_E_ARG) return st;
+    *n_out = 0;
+    if (groups_total_out) *groups_total_out = 0;
+    if (st || empty) return st;
+    int64_t nd = 0;
+    if ((st = stream_merge(s, &nd)) || nd == 0) return st;
+    if ((st = stream_rank(s, nd, k))) return st;
+    const int64_t m = std::min(nd, k);
+    hm_launch_top_narrow(s->ctx->stream, (const uint64_t*)s->tk.p, (const uint64_t*)s->tc.p, (uint64_t)m, groups_out,
+                         counts_out);
+    HIPCHK(hipGetLastError());
+    *n_out = m;
+    if (groups_total_out) *groups_total_out = nd;
+    return HM_OK;
 }
 
 /* a raster's tiles, group and log into the kernel's struct: everything but
@@ -1335,7 +1424,7 @@ extern "C" int hm_stream_destroy(hm_stream* s)
     if (s->ctx && s->ctx->stream) (void)hipStreamSynchronize(s->ctx->stream);
     for (void* p : {(void*)s->state, (void*)s->bk.keys, (void*)s->bk_alt, (void*)s->bflag, (void*)s->blist,
                     (void*)s->bloc, s->bids.p, s->rec.p, s->plat.p, s->plon.p, s->pkeep.p, s->pstart.p, s->rk.p,
-                    s->rc.p, s->mk.p, s->mc.p})
+                    s->rc.p, s->mk.p, s->mc.p, s->tk.p, s->tc.p})
         if (p) (void)hipFree(p);
     log_free(s, s->log);
     log_free(s, s->alt);

@@ -30,6 +30,12 @@ label is a device rollup of the hour buckets:
                                growth through hm_raster_accumulate;
                                tile_series(...) the tiles' points per frame and
                                tile_frame_images(...) the frames on one scale
+  top(k, rects, hours, group)  the k hottest cells of a view in rank order (count
+                               descending, then zoom, row, col), selected on the
+                               device (hm_stream_top); top_tiles(k, zoom, ...)
+                               the busiest cells of one zoom, top_groups /
+                               top_users(k, rects, hours) the most active groups
+                               there (hm_stream_top_groups)
   expire(before_hour)         retention: the cells of hours < before_hour
                                leave the stream, their buckets are freed
   forget(users, groups, hours)  erasure: the cells of these users or group
@@ -71,6 +77,7 @@ import numpy as np
 from . import _lib, device
 from . import heatmap as _hm
 from . import raster as _raster
+from . import top as _top
 
 ALLTIME = -1
 EACH_HOUR = -2
@@ -753,6 +760,143 @@ class StreamingHeatmap:
         """Cells of every kept point inside the rectangles (and the hours)."""
         _, z, r, c, cnt = self.view(rects, hours, "merged")
         return device.Counts(z, r, c, cnt, 0, [])
+
+    # ------------------------------------------------------------- rankings
+
+    def top_device(self, k, rects, hours=None, group="merged"):
+        """(n, keys, counts, cells): of the `cells` distinct summed cells that
+        view_device(rects, hours, group) would return, the first n = min(k,
+        cells) in rank order (count descending, then HM_KEY ascending) as
+        int64 CUDA tensors of n entries (hm_stream_top: the view's filter and
+        merge, then a device selection that emits k cells, not all of them).
+        group is 'merged' or one group id; out-of-square cells not included."""
+        torch = self._torch
+        self.ctx.bind_stream()
+        k = _top.check_k(k)
+        if group == "each":
+            raise ValueError("a ranking takes group='merged' or one group id (a ranking per group is out of reach "
+                             "of one call: rank each group's id in turn)")
+        rects, lo, hi, gw = self._view_args(rects, hours, group)
+        ra = (ctypes.c_int64 * (5 * len(rects)))(*[v for r in rects for v in r])
+        dev = "cuda:%d" % self.device_index
+        keys = torch.empty(k, dtype=torch.int64, device=dev)
+        counts = torch.empty(k, dtype=torch.int64, device=dev)
+        n, cells = ctypes.c_int64(0), ctypes.c_int64(0)
+        rc = self.ctx.L.hm_stream_top(self.ptr, lo, hi, gw, ra, len(rects), k, device._ptr(keys), device._ptr(counts),
+                                      ctypes.byref(n), ctypes.byref(cells))
+        _lib.raise_for(rc)
+        return n.value, keys[:n.value], counts[:n.value], cells.value
+
+    def top(self, k, rects, hours=None, group="merged"):
+        """Host arrays (zoom, row, col, count) of the k hottest cells inside
+        the rectangles (and hours, and group), in rank order: count
+        descending, then zoom, row, col ascending.  The out-of-square side
+        records inside the rectangles as given (not clipped, as view's) take
+        part."""
+        n, keys, counts, _ = self.top_device(k, rects, hours, group)
+        z, r, c = device.decode_keys(keys.cpu().numpy().view(np.uint64))
+        side = None
+        if len(self._x):
+            side = _view_records(self._x, [tuple(int(v) for v in q) for q in rects], hours, group).T[1:]
+        return _top.join_ranked(z, r, c, counts.cpu().numpy(), side, k)
+
+    def top_tiles(self, k, zoom, hours=None, user=None, within=None):
+        """[((zoom, row, col), count)]: the k busiest cells of one zoom, in
+        rank order -- of the whole zoom, or only inside the heatmap tiles
+        within = [(tz, tr, tc)] (1..HM_VIEW_MAX_RECTS of them, tz <= zoom) --
+        for every kept point (user = None) or the group label `user` (an
+        unknown label: no cells)."""
+        zoom = int(zoom)
+        if not self.zmin <= zoom <= self.zmax:
+            raise ValueError("zoom %d is outside the stream's %d..%d" % (zoom, self.zmin, self.zmax))
+        if within is None:
+            rects = [(zoom, 0, 1 << zoom, 0, 1 << zoom)]
+        else:
+            tiles = [tuple(int(v) for v in t) for t in within]
+            if not 1 <= len(tiles) <= _lib.HM_VIEW_MAX_RECTS or any(len(t) != 3 for t in tiles):
+                raise ValueError("within takes 1..%d tiles (tz, tr, tc)" % _lib.HM_VIEW_MAX_RECTS)
+            for tz, tr, tc in tiles:
+                if not 0 <= tz <= zoom or not (0 <= tr < (1 << tz) and 0 <= tc < (1 << tz)):
+                    raise ValueError("tile %r is not a tile of zooms 0..%d inside the square" % ((tz, tr, tc), zoom))
+            rects = tile_rects(tiles, 0)
+            rects = [(zoom, rlo << (zoom - z), rhi << (zoom - z), clo << (zoom - z), chi << (zoom - z))
+                     for z, rlo, rhi, clo, chi in rects]
+        # the group word as tile_raster resolves it
+        gw = _raster_args(self.zmin, self.zmax, self._index, [(zoom, 0, 0)], hours, user, 0, 0)[3]
+        _top.check_k(k)
+        if gw is None:
+            return []
+        z, r, c, n = self.top(k, rects, hours, "merged" if gw == _lib.HM_VIEW_MERGED else gw)
+        return [((int(a), int(b), int(d)), int(e)) for a, b, d, e in zip(z, r, c, n)]
+
+    def _top_groups_device(self, k, rects, lo, hi):
+        torch = self._torch
+        ra = (ctypes.c_int64 * (5 * len(rects)))(*[v for r in rects for v in r])
+        dev = "cuda:%d" % self.device_index
+        ids = torch.empty(k, dtype=torch.int32, device=dev)
+        counts = torch.empty(k, dtype=torch.int64, device=dev)
+        n, total = ctypes.c_int64(0), ctypes.c_int64(0)
+        rc = self.ctx.L.hm_stream_top_groups(self.ptr, lo, hi, ra, len(rects), k, device._ptr(ids),
+                                             device._ptr(counts), ctypes.byref(n), ctypes.byref(total))
+        _lib.raise_for(rc)
+        return (ids[:n.value].cpu().numpy().view(np.uint32).astype(np.int64), counts[:n.value].cpu().numpy(),
+                total.value)
+
+    def top_groups(self, k, rects, hours=None):
+        """Host arrays (group ids uint32, points): the k most active groups
+        inside the rectangles (all of one zoom) and hours, by their kept
+        points there -- count descending, then id ascending; the points
+        without a group rank as id 0xFFFFFFFE.  A cell in several rectangles
+        counts once.  Out-of-square side records inside the rectangles as
+        given are counted (hm_stream_top_groups)."""
+        self.ctx.bind_stream()
+        k = _top.check_k(k)
+        rects, lo, hi, _ = self._view_args(rects, hours, "merged")
+        if len({r[0] for r in rects}) != 1:
+            raise ValueError("the rectangles of a group ranking must be of one zoom: every point is counted once per "
+                             "zoom")
+        side = _view_records(self._x, rects, hours, "each") if len(self._x) else np.zeros((0, 5), np.int64)
+        extra = {}
+        for g, n in zip(side[:, 0].tolist(), side[:, 4].tolist()):
+            extra[g] = extra.get(g, 0) + n
+        ids, counts, total = self._top_groups_device(min(_lib.HM_TOP_MAX_K, k + len(extra)), rects, lo, hi)
+        if extra:
+            # a group with side records ranks by both parts: its device part
+            # when the ranking did not reach it is one group-select view
+            have = dict(zip(ids.tolist(), counts.tolist()))
+            for g, n in extra.items():
+                if g not in have and total > len(ids):
+                    nv, _, vc, _ = self.view_device(rects, hours, int(g))
+                    have[g] = int(vc[:nv].sum().item())
+                have[g] = have.get(g, 0) + n
+            ids = np.fromiter(have.keys(), np.int64, len(have))
+            counts = np.fromiter(have.values(), np.int64, len(have))
+            order = _top.rank_order(ids, counts)[:k]
+            ids, counts = ids[order], counts[order]
+        return ids[:k].astype(np.uint32), counts[:k]
+
+    def top_users(self, k, rects, hours=None):
+        """[(label, points)]: the k most active user groups inside the
+        rectangles and hours, in rank order (top_groups without the points
+        that have no group: it asks for k + 1 groups and drops that entry; at
+        k = HM_TOP_MAX_K, when the entry took one of the places, the totals
+        come from a per-group view instead)."""
+        k = _top.check_k(k)
+        if self._explicit_max >= len(self.labels):
+            raise ValueError("rows need a label per group: group id %d was passed as group= and has none "
+                             "(feed the stream with user_id= to build rows)" % self._explicit_max)
+        if k < _lib.HM_TOP_MAX_K:
+            ids, counts = self.top_groups(k + 1, rects, hours)
+        else:
+            ids, counts = self.top_groups(k, rects, hours)
+            if len(ids) == k and NOGROUP in ids.tolist():
+                # k + 1 groups are out of a ranking's reach and the no-group entry took a place: every
+                # group's total from a view, as before there were rankings
+                g, _, _, _, n = self.view(rects, hours, "each")
+                tot = _sum_records(np.stack([g.astype(np.int64), n.astype(np.int64)], axis=1), 1)
+                order = _top.rank_order(tot[:, 0], tot[:, 1])
+                ids, counts = tot[order, 0], tot[order, 1]
+        return [(self.labels[g], int(n)) for g, n in zip(ids.tolist(), counts.tolist()) if g != NOGROUP][:k]
 
     def tile_cells(self, tiles, hours=None, label=None, user=None, max_zoom_level=None, delta=None) -> "_hm.Cells":
         """The bins of the rows of the heatmap row tiles [(tz, tr, tc)]: those

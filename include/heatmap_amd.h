@@ -515,6 +515,62 @@ int hm_stream_raster_frames(hm_stream* s, int64_t hour_lo, int64_t hour_hi, int6
 int hm_raster_accumulate(hm_ctx* ctx, const uint64_t* grid_in, int64_t nframes, int64_t frame_elems,
                          int64_t window, uint64_t* grid_out);
 
+/* Rankings: the k hottest cells, the k most active groups ("where is it
+ * hottest right now", "who is most active here").  One order, everywhere:
+ * record a ranks before record b when count_a > count_b, or the counts are
+ * equal and key_a < key_b, both compared as unsigned 64-bit.  For cells the
+ * key is HM_KEY(zoom, row, col), so ties go by zoom, then row, then column;
+ * for groups it is the group id.  Over distinct keys that is a total order:
+ * every result is unique, order included.  The selection runs on the device
+ * (a radix walk to the k-th count and, among the ties there, to the last key
+ * taken; a collect; a sort of the <= HM_TOP_MAX_K chosen records) and emits
+ * k records, where a view followed by a sort emits and sorts every one.
+ *
+ *   hm_cells_top      the first min(n, k) of n records (device arrays: any
+ *                     distinct u64 keys, any u64 counts, zero and values >=
+ *                     2^63 included; hm_count, rollup, window and view output)
+ *                     in rank order into keys_out / counts_out (device, k
+ *                     entries; those at and beyond *n_out are untouched).
+ *                     Repeated keys are not merged, each record ranks by
+ *                     itself.  *n_out = min(n, k) is written at once; the call
+ *                     is asynchronous on the context's stream and reads
+ *                     nothing back.  The inputs are left unchanged.  n = 0 is
+ *                     HM_OK with nothing written.  HM_E_ARG, outputs
+ *                     untouched: a null context or n_out, n < 0, k outside 1
+ *                     .. HM_TOP_MAX_K, a null array when n > 0, output ranges
+ *                     that overlap the inputs or each other.  Scratch comes
+ *                     from the context (HM_E_NOMEM when it cannot; then, and
+ *                     after HM_E_HIP, *n_out is untouched as well).
+ *   hm_stream_top     the selection of hm_stream_view -- rectangles, clipping,
+ *                     hours or the alltime pair, group = HM_VIEW_MERGED or one
+ *                     group id 0 .. 0xFFFFFFFE -- and of its N distinct summed
+ *                     cells the first min(k, N) in rank order (device arrays of
+ *                     k entries, keys in hm_count's layout).  *n_out is that
+ *                     number, *cells_out (may be NULL) is N.  HM_E_ARG, outputs
+ *                     untouched: whatever hm_stream_view refuses, HM_VIEW_EACH,
+ *                     k outside 1 .. HM_TOP_MAX_K, a null output.
+ *                     HM_E_CAPACITY when no bucket is left for the query's
+ *                     label, as a view.  An empty selection is HM_OK with 0,
+ *                     0.  The log is left exactly as it is.  Waits once (the
+ *                     merge's read-back).
+ *   hm_stream_top_groups  the group ids ranked by their kept points inside
+ *                     the rectangles and hours: a group's total is the sum of
+ *                     the counts of its cells in the rectangles, a cell in
+ *                     several rectangles counted once.  Every point is counted
+ *                     once per zoom, so all rectangles must be of one zoom
+ *                     (else HM_E_ARG).  The cells without a group rank as id
+ *                     0xFFFFFFFE.  The first min(k, G) of the G groups present
+ *                     go to groups_out (device u32[k]) and counts_out (device
+ *                     u64[k]); *n_out is that number, *groups_total_out (may
+ *                     be NULL) is G.  Other rules as hm_stream_top. */
+#define HM_TOP_MAX_K 4096
+int hm_cells_top(hm_ctx* ctx, const uint64_t* keys, const uint64_t* counts, int64_t n, int64_t k,
+                 uint64_t* keys_out, uint64_t* counts_out, int64_t* n_out);
+int hm_stream_top(hm_stream* s, int64_t hour_lo, int64_t hour_hi, int64_t group, const int64_t* rects, int nrects,
+                  int64_t k, uint64_t* keys_out, uint64_t* counts_out, int64_t* n_out, int64_t* cells_out);
+int hm_stream_top_groups(hm_stream* s, int64_t hour_lo, int64_t hour_hi, const int64_t* rects, int nrects,
+                         int64_t k, uint32_t* groups_out, uint64_t* counts_out, int64_t* n_out, int64_t* groups_total_out);
+
 /* Multi-GPU exchange of hm_count cells (one process per GPU; the collectives
  * are RCCL calls made by the caller, heatmap_amd/multigpu.py).  They replace
  * the reference's two shuffles, reduceByKey (heatmap.py:111) and groupByKey

@@ -103,6 +103,21 @@ import.  Host ms around each call, which ends in its own wait; 2 warm-up
 repetitions dropped.  --expire-only times the expire alone (no newer API is
 needed, so a checkout of the parent commit can run it); --parent-json FILE puts
 that run's times into this one's result as "parent_expire_ms".
+
+--retain H --top ranks on the steady retained log, each ranking against the
+route a caller had before it: the 100 hottest zoom-14 cells of the trailing 24
+hours (top_device against view_device, a two-key device sort with torch and a
+slice of 100), the same inside the 4 x 3-tile screen of --raster at its detail
+zoom, and the 10 most active groups on that screen (hm_stream_top_groups
+against view_device(..., 'each'), a per-group sum and the sort) on the same
+cells imported with group = a hash of the cell % 1000.  Both routes are warmed,
+then take TOP_REPS alternating repetitions; host ms around each, which ends in
+a synchronise; median and min-max of each, and "not distinguishable" when the
+ranges overlap; for the two cell rankings also the selection alone
+(hm_cells_top) against the sort alone, on the view's cells.  --sort-only times the earlier route alone (nothing newer than
+hm_stream_view and hm_stream_import is needed, so a checkout of the parent
+commit can run it); --parent-json FILE puts that run's times into this one's
+result as "parent_sort_ms".
 """
 import argparse
 import json
@@ -646,6 +661,130 @@ def forget_bench(s, a, lo, hi):
     return out
 
 
+TOP_REPS = 25
+
+
+def _two_key_top(keys, counts, k):
+    """the first k of (keys, counts) by count descending, then key ascending: two stable device sorts"""
+    ks, i = torch.sort(keys, stable=True)
+    cs, j = torch.sort(counts[i], descending=True, stable=True)
+    return ks[j][:k], cs[:k]
+
+
+def top_bench(s, a, lo, hi):
+    """--top / --sort-only (module docstring) on the stream as it stands"""
+    import ctypes
+
+    L = s.ctx.L
+    h24 = (max(lo, hi - 24), hi)
+    n, keys, counts, _ = s.window_device(*h24)
+    k18 = keys[:n][(keys[:n] >> 58) == a.zmax]
+    c18 = counts[:n][(keys[:n] >> 58) == a.zmax]
+    heavy = int(k18[torch.argmax(c18)].item())
+    del keys, counts, k18, c18
+    r, c = (heavy >> 29) & 0x1FFFFFFF, heavy & 0x1FFFFFFF
+    tr, tc = (r >> 8) - 1, (c >> 8) - 1
+    screen = [(a.zmax, (tr + i) << 8, (tr + i + 1) << 8, (tc + j) << 8, (tc + j + 1) << 8)
+              for i in range(3) for j in range(4)]
+    zw = min(14, a.zmax)
+    out = {"hours": list(h24), "reps": TOP_REPS, "log_cells": s.cells()[0],
+           "timing": "host ms around the route plus one synchronise; both routes warmed, then alternating"}
+    # the groups: the log's cells under group = a hash of the cell % 1000, in a stream of their own
+    ne, ek, ec, eg, eh = s.export_device()
+    g1000 = ((ek[:ne] ^ (ek[:ne] >> 23)) * 2654435761 % 1000).to(torch.int32)
+    g = StreamingHeatmap(a.zmin, a.zmax, base_hour=BASE, initial_cells=max(1024, ne))
+    rc = L.hm_stream_import(g.ptr, ek.data_ptr(), ec.data_ptr(), g1000.data_ptr(), eh.data_ptr(), ne, 1)
+    assert rc == 0, rc
+    del ek, ec, eg, eh
+
+    def sort_cells(rects, k):
+        nv, vk, vc, _ = s.view_device(rects, h24)
+        return (nv, *_two_key_top(vk[:nv], vc[:nv], k))
+
+    def sort_groups(rects, k):
+        nv, vk, vc, vg = g.view_device(rects, h24, "each")
+        ids, inv = torch.unique(vg[:nv], return_inverse=True)
+        tot = torch.zeros(ids.numel(), dtype=torch.int64, device="cuda").scatter_add_(0, inv, vc[:nv])
+        return (ids.numel(), *_two_key_top(ids.to(torch.int64) & 0xFFFFFFFF, tot, k))
+
+    gi = torch.empty(16, dtype=torch.int32, device="cuda")
+    gc = torch.empty(16, dtype=torch.int64, device="cuda")
+    n64, t64 = ctypes.c_int64(0), ctypes.c_int64(0)
+
+    def top_groups(rects, k):
+        ra = (ctypes.c_int64 * (5 * len(rects)))(*[v for q in rects for v in q])
+        rc = L.hm_stream_top_groups(g.ptr, h24[0], h24[1], ra, len(rects), k, gi.data_ptr(), gc.data_ptr(),
+                                    ctypes.byref(n64), ctypes.byref(t64))
+        assert rc == 0, rc
+        return t64.value, gi[:n64.value].to(torch.int64) & 0xFFFFFFFF, gc[:n64.value]
+
+    def top_cells(rects, k):
+        nt, tk, tcnt, total = s.top_device(k, rects, h24)
+        return total, tk, tcnt
+
+    cases = [("a_whole_z%d_top100" % zw, [(zw, 0, 1 << zw, 0, 1 << zw)], 100, sort_cells, top_cells),
+             ("b_screen_4x3_tiles_z%d_top100" % a.zmax, screen, 100, sort_cells, top_cells),
+             ("c_screen_4x3_tiles_top_groups10", screen, 10, sort_groups, top_groups)]
+    ok = True
+    for name, rects, k, old, new in cases:
+        routes = [("sort_ms", old)] + ([] if a.sort_only else [("top_ms", new)])
+        t = {key: [] for key, _ in routes}
+        last = {}
+        for key, f in routes:
+            f(rects, k)                       # warm: code objects, the capacity memo, the scratch
+            f(rects, k)
+        for _ in range(TOP_REPS):
+            for key, f in routes:
+                ms, last[key] = _ms(lambda: f(rects, k))
+                t[key].append(ms)
+        res = {"rects": [list(map(int, q)) for q in rects], "k": k, "selected": int(last["sort_ms"][0])}
+        for key in t:
+            res[key] = _stats(t[key])
+        if not a.sort_only:
+            same = all(torch.equal(x, y) for x, y in zip(last["sort_ms"][1:], last["top_ms"][1:])) and \
+                last["sort_ms"][0] == last["top_ms"][0] and last["top_ms"][1].numel() == min(k, last["top_ms"][0])
+            ok &= bool(same)
+            res["top_equals_sorted_view"] = bool(same)
+            o, w = res["sort_ms"], res["top_ms"]
+            res["verdict"] = ("not distinguishable" if w["min"] <= o["max"] and o["min"] <= w["max"] else
+                              "top faster" if w["median"] < o["median"] else "top slower")
+            if new is top_cells:
+                # the selection by itself against the sort by itself, on the view's cells (filter and merge left out)
+                nv, vk, vc, _ = s.view_device(rects, h24)
+                vk, vc = vk[:nv].clone(), vc[:nv].clone()
+                ko, co = torch.empty(k, dtype=torch.int64, device="cuda"), torch.empty(k, dtype=torch.int64, device="cuda")
+
+                def select_alone():
+                    rc = L.hm_cells_top(s.ctx.ptr, vk.data_ptr(), vc.data_ptr(), nv, k, ko.data_ptr(), co.data_ptr(),
+                                        ctypes.byref(n64))
+                    assert rc == 0, rc
+
+                ta = {"select_alone_ms": [], "sort_alone_ms": []}
+                for rep in range(TOP_REPS + 2):
+                    ta["select_alone_ms"].append(_ms(select_alone)[0])
+                    ta["sort_alone_ms"].append(_ms(lambda: _two_key_top(vk, vc, k))[0])
+                sk, sc = _two_key_top(vk, vc, k)
+                ok &= bool(torch.equal(sk, ko) and torch.equal(sc, co))
+                for key in ta:
+                    res[key] = _stats(ta[key][2:])
+        out[name] = res
+    g.close()
+    if not a.sort_only:
+        out["check"] = "ok" if ok else "FAIL"
+    if a.parent_json:
+        pj = json.load(open(a.parent_json))["top"]
+        assert pj["log_cells"] == out["log_cells"] and pj["hours"] == out["hours"]
+        for name, *_ in cases:
+            assert pj[name]["selected"] == out[name]["selected"]
+            out[name]["parent_sort_ms"] = pj[name]["sort_ms"]
+            o, w = pj[name]["sort_ms"], out[name]["top_ms"]
+            out[name]["verdict_vs_parent"] = ("not distinguishable" if w["min"] <= o["max"] and o["min"] <= w["max"]
+                                              else "top faster" if w["median"] < o["median"] else "top slower")
+        out["parent_sort_note"] = ("this script with --top --sort-only run by a checkout of the parent commit (its "
+                                   "library and package) on the same seeded log, in the same session")
+    return out
+
+
 def retain(a):
     """--retain H: a stream under retention (module docstring)"""
     n, H = int(a.batch), a.retain
@@ -679,6 +818,7 @@ def retain(a):
     ras = raster_bench(s, a, BASE + total - 1 - H, BASE + total) if a.raster else None
     fra = frames_bench(s, a, BASE + total) if a.frames else None
     fgt = forget_bench(s, a, BASE + total - 1 - H, BASE + total) if a.forget or a.expire_only else None
+    top = top_bench(s, a, BASE + total - 1 - H, BASE + total) if a.top or a.sort_only else None
     result = json.dumps({
         "metric": "stream under retention: expire(newest - H) and window(newest - H, newest + 1) per one-hour batch",
         "retain_hours": H, "batch_points": n, "batches": a.batches, "warmup": a.warmup, "zooms": [a.zmin, a.zmax],
@@ -696,6 +836,7 @@ def retain(a):
         "raster": ras,
         "frames": fra,
         "forget": fgt,
+        "top": top,
         "series": series,
         "data": "synthetic (heatmap_amd.synth, generated on device, resident in HBM)"})
     print(result)
@@ -735,13 +876,18 @@ def main():
                     help="with --retain: forget and selective export on the steady log against expire, the full "
                          "export and export + mask + import (module docstring)")
     ap.add_argument("--expire-only", action="store_true", help="with --retain: --forget's expire alone")
+    ap.add_argument("--top", action="store_true",
+                    help="with --retain 24 or more: the 100 hottest cells and the 10 most active groups against a view "
+                         "and a device sort (module docstring)")
+    ap.add_argument("--sort-only", action="store_true", help="with --retain: --top's view-and-sort routes alone")
     ap.add_argument("--readd-only", action="store_true",
                     help="with --retain: time only the re-adding of the retained batches to a fresh stream")
     ap.add_argument("--parent-json", default=None, metavar="FILE",
                     help="with --view: a --window-only result of the parent commit, kept as parent_window; with "
                          "--snapshot: its --readd-only result, kept as parent_readd_ms; with --raster: its "
                          "--view-only result, kept as parent_view_ms; with --frames: its --loop-only result, kept as "
-                         "parent_loop_ms; with --forget: its --expire-only result, kept as parent_expire_ms")
+                         "parent_loop_ms; with --forget: its --expire-only result, kept as parent_expire_ms; with "
+                         "--top: its --sort-only result, kept as parent_sort_ms")
     ap.add_argument("--out", default=None, metavar="FILE", help="with --retain: also write the JSON line to FILE")
     a = ap.parse_args()
     if a.retain > 0:
