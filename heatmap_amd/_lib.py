@@ -45,7 +45,7 @@ EXPORTS = ["hm_abi_version", "hm_status_string", "hm_ctx_create", "hm_ctx_set_st
            "hm_stream_window", "hm_stream_view", "hm_stream_expire", "hm_stream_export", "hm_stream_import",
            "hm_stream_destroy", "hm_stream_raster", "hm_cells_raster", "hm_raster_render",
            "hm_stream_raster_frames", "hm_raster_accumulate", "hm_stream_forget", "hm_stream_export_select",
-           "hm_cells_top", "hm_stream_top", "hm_stream_top_groups",
+           "hm_cells_top", "hm_stream_top", "hm_stream_top_groups", "hm_stream_visitors",
            "hm_dense_grid_size", "hm_cells_route", "hm_cells_merge", "hm_cells_merge_runs",
            "hm_cells_route_pieces", "hm_cells_merge_pieces", "hm_dense_cells", "hm_format_bins", "hm_format_ids", "hm_bench_read"]
 
@@ -142,6 +142,8 @@ def load() -> ctypes.CDLL:
                                     P(c.c_int64), P(c.c_int64)]
         L.hm_stream_top_groups.argtypes = [vp, c.c_int64, c.c_int64, P(c.c_int64), c.c_int, c.c_int64, vp, vp,
                                            P(c.c_int64), P(c.c_int64)]
+        L.hm_stream_visitors.argtypes = [vp, c.c_int64, c.c_int64, P(c.c_int64), c.c_int, c.c_int64, vp, vp, vp,
+                                         c.c_int64, P(c.c_int64), P(c.c_int64)]
         L.hm_dense_grid_size.argtypes = [c.c_int]
         L.hm_dense_grid_size.restype = c.c_int64
         L.hm_cells_route.argtypes = [vp, vp, vp, c.c_int64, c.c_int, c.c_int, c.c_int, vp, vp, vp, c.c_int,

@@ -571,7 +571,8 @@ void hm_launch_synth(hipStream_t s, int kind, uint64_t seed, int64_t start, int6
 enum {
     HMS_ST_OCCUPIED = 0, HMS_ST_OVERFLOW = 1, HMS_ST_CURSOR = 2, HMS_ST_BUCKETS = 3, HMS_ST_BFULL = 4,
     HMS_ST_EXOTIC = 5, HMS_ST_BMM = 6 /* a bucket of the batch (the only one if NLIST == 1) */, HMS_ST_NLIST = 7,
-    HMS_ST_ERR = 8 /* first bad hour: index << 8 | HM_E_RANGE */, HMS_ST_COUNT = 16
+    HMS_ST_ERR = 8 /* first bad hour: index << 8 | HM_E_RANGE */,
+    HMS_ST_WCELLS = 9, HMS_ST_WPOINTS = 10 /* hm_stream_visitors: the cells and points withheld */, HMS_ST_COUNT = 16
 };
 #define HMS_MAX_PARTS 64                 /* batches of more buckets take the grouped general path */
 #define HMS_NOGROUP 0xFFFFFFFEu          /* kept points without a user group */
@@ -853,6 +854,28 @@ void hm_launch_stream_view(hipStream_t s, const HmsViewArgs& a);
  * gmode is not read: every group passes) */
 void hm_launch_stream_view_groups(hipStream_t s, const HmsViewArgs& a);
 void hm_launch_stream_expire(hipStream_t s, const HmsExpireArgs& a);
+/* distinct visitors per cell (hm_stream_visitors, hm_visit.h): a view's merged
+ * (group label, cell) records folded per cell into a table -- slot j holds the
+ * cell and its points, visitors[j] the records met, one per group -- and the
+ * table swept with the threshold applied */
+struct HmsVisitArgs {
+    const uint64_t* keys;    /* n distinct label bucket << cb | cell records (stream_merge) */
+    const uint64_t* counts;
+    uint64_t n;
+    int cb, zmin, zmax;
+    HmsTable table;          /* hm_visit_slots(n) slots, empty; state: the stream's (HMS_ST_OVERFLOW) */
+    uint32_t* visitors;      /* one word per slot, zeroed */
+    uint64_t min_visitors;
+    uint64_t* keys_out;      /* hm_count layout; the first `capacity` emitted cells are written */
+    uint64_t* points_out;
+    uint32_t* visitors_out;  /* or NULL */
+    uint64_t capacity;
+    unsigned long long* cursor;   /* counts every emitted cell */
+};
+/* the fold: every slot's points and visitors complete when it ends */
+void hm_launch_stream_visit_fold(hipStream_t s, const HmsVisitArgs& a);
+/* the sweep: emitted cells out, state[HMS_ST_WCELLS / HMS_ST_WPOINTS] += the withheld */
+void hm_launch_stream_visit_emit(hipStream_t s, const HmsVisitArgs& a);
 /* the occupied slots of a bucket table -> list, their number added to *n */
 void hm_launch_stream_occupied(hipStream_t s, const HmsBuckets& b, uint32_t* list, unsigned long long* n);
 

@@ -37,6 +37,10 @@
  * selection (hm_top.hip) before the emit, so k cells leave, not all of them;
  * a ranking of groups (hm_stream_top_groups) keys the survivors by group alone
  * (k_stream_view_groups) before the same merge and selection.
+ * Distinct visitors (hm_stream_visitors) are a per-group view whose merged
+ * (group, cell) records are folded once more, per cell, into points and a
+ * count of groups (k_stream_visit_fold), and listed above a threshold
+ * (k_stream_visit_emit): the k-anonymous cells of a selection.
  * Retention (hm_stream_expire, k_stream_expire)
  * filters the log into the alternate arrays and moves the surviving buckets
  * to a fresh bucket table, which frees the slots of the expired hours and of
@@ -58,6 +62,8 @@
 #include "hm_table.h"
 #define HMS_SELECT_FN __device__ __forceinline__   /* hms_select_has on the device */
 #include "hm_stream_select.h"
+#define HM_VISIT_FN __device__ __forceinline__   /* hm_visit_judge on the device */
+#include "hm_visit.h"
 
 __device__ __forceinline__ uint64_t hms_pyr_off(int z) { return ((1ull << (2 * z)) - 1ull) / 3ull; }
 
@@ -769,6 +775,120 @@ __global__ __launch_bounds__(256) void k_stream_view_groups(HmsViewArgs a)
     }
 }
 
+/* Distinct visitors per cell (hm_stream_visitors), the second fold: the view's
+ * merged records are distinct (group label, cell) pairs, so a cell's visitors
+ * are the records that name it and its points their counts' sum.  One pass,
+ * a record per lane: the bucket bits are stripped, the cell is inserted into
+ * the table and its slot (hms_insert_slot) indexes the visitors array beside
+ * it.  A low-zoom cell is named by every group -- the whole of zoom 0 is one
+ * slot -- so the equal cells of a wave row are summed before the table is
+ * touched: the first HMS_VF_TURNS distinct cells of a row each cost one probe
+ * and one atomic pair for all their lanes (a turn that finds its cell on one
+ * lane only reduces nothing), the others go on as they are. */
+#define HMS_VF_TURNS 4
+__global__ __launch_bounds__(256) void k_stream_visit_fold(HmsVisitArgs a)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t cmask = (1ull << a.cb) - 1ull;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;   /* a multiple of 64: i0 is wave-uniform */
+    uint32_t overflow = 0;
+    for (uint64_t i0 = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) & ~63ull; i0 < a.n; i0 += stride) {
+        const uint64_t i = i0 + lane;
+        const bool in = i < a.n;
+        const uint64_t cell = in ? a.keys[i] & cmask : 0ull;
+        uint64_t pts = in ? a.counts[i] : 0ull;
+        uint32_t vis = in ? 1u : 0u;
+        bool head = in;               /* this lane inserts (pts, vis) */
+        uint64_t left = __ballot(in);
+        for (int turn = 0; turn < HMS_VF_TURNS && left; turn++) {
+            const int leader = __ffsll((unsigned long long)left) - 1;
+            const uint64_t c0 = __shfl((unsigned long long)cell, leader, 64);
+            const bool mine = ((left >> lane) & 1ull) && cell == c0;
+            const uint64_t m = __ballot(mine);
+            if (__popcll(m) > 1) {    /* (wave-uniform) */
+                uint64_t t = mine ? pts : 0ull;
+#pragma unroll
+                for (int d = 32; d >= 1; d >>= 1) t += __shfl_xor((unsigned long long)t, d, 64);
+                if ((int)lane == leader) {
+                    pts = t;
+                    vis = (uint32_t)__popcll(m);
+                } else if (mine) {
+                    head = false;
+                }
+            }
+            left &= ~m;
+        }
+        if (head) {
+            const uint64_t slot = hms_insert_slot(a.table, cell, pts, &overflow);
+            if (slot != ~0ull) atomicAdd(&a.visitors[slot], vis);
+        }
+    }
+    const uint64_t of = hms_wave_sum(overflow);   /* cannot happen: the table has twice the records' slots */
+    if (lane == 0 && of) atomicAdd(&a.table.state[HMS_ST_OVERFLOW], (unsigned long long)of);
+}
+
+/* The threshold and the emit: the table swept in k_table_extract's manner.  A
+ * block takes 256 * HMS_VE_U slots at a time (their loads and their visitors'
+ * issued together), judges the occupied ones (hm_visit_judge), counts the
+ * emitted (one block scan, one atomic on the cursor per chunk that holds any)
+ * and ranks them row by row; those that land below `capacity` are written as
+ * (HM_KEY, points, visitors).  The cursor counts every emitted cell, so one
+ * launch gives the records and the size a larger call needs.  The withheld
+ * cells and points are summed per thread and leave as one atomic pair per
+ * block. */
+#define HMS_VE_U 8
+__global__ __launch_bounds__(256) void k_stream_visit_emit(HmsVisitArgs a)
+{
+    constexpr int U = HMS_VE_U;
+    __shared__ uint32_t scr[256 / 64 + 1];
+    __shared__ unsigned long long sbase;
+    const int tid = threadIdx.x;
+    const ulonglong2* slots = (const ulonglong2*)a.table.slots;
+    const uint64_t ns = a.table.mask + 1;
+    HmVisitWithheld wh = {0, 0};
+    constexpr uint64_t CH = 256 * U;
+    for (uint64_t c0 = (uint64_t)blockIdx.x * CH; c0 < ns; c0 += (uint64_t)gridDim.x * CH) {
+        ulonglong2 sl[U];
+        uint32_t v[U];
+        bool sel[U];
+        uint32_t cnt = 0;
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const uint64_t i = c0 + (uint64_t)u * 256 + tid;
+            sl[u] = i < ns ? slots[i] : make_ulonglong2(HMS_EMPTY, 0ull);
+            v[u] = i < ns ? a.visitors[i] : 0u;
+        }
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            sel[u] = sl[u].x != HMS_EMPTY && hm_visit_judge(&wh, v[u], sl[u].y, a.min_visitors);
+            cnt += sel[u];
+        }
+        uint32_t tot;
+        const uint32_t pos = hm_block_excl_scan<256>(cnt, scr, &tot);
+        if (tid == 0) sbase = tot ? atomicAdd(a.cursor, (unsigned long long)tot) : 0ull;
+        __syncthreads();
+        uint64_t wq = sbase + __shfl(pos, 0, 64);
+        __syncthreads();
+        if (!tot || wq >= a.capacity) continue;   /* (wave-uniform; no barrier below) */
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const uint64_t inb = __ballot(sel[u]);
+            const uint64_t q = wq + hm_mbcnt(inb);
+            wq += (uint64_t)__popcll(inb);
+            if (sel[u] && q < a.capacity) {
+                a.keys_out[q] = hms_cell_key_log(sl[u].x, a.zmin, a.zmax);
+                a.points_out[q] = sl[u].y;
+                if (a.visitors_out) a.visitors_out[q] = v[u];
+            }
+        }
+    }
+    uint64_t w[2] = {wh.cells, wh.points};
+    hms_block_sums(w);
+    if (tid == 0 && w[0]) {
+        atomicAdd(&a.table.state[HMS_ST_WCELLS], (unsigned long long)w[0]);
+        atomicAdd(&a.table.state[HMS_ST_WPOINTS], (unsigned long long)w[1]);
+    }
+}
 
 /* is a raw bucket key inside a raster's hours and group */
 __device__ __forceinline__ bool hms_raster_in(const HmsRasterArgs& a, uint64_t bk)
@@ -1375,6 +1495,17 @@ void hm_launch_stream_view_groups(hipStream_t s, const HmsViewArgs& a)
     const uint64_t chunks = (a.n + 256 * HMS_VW_U - 1) / (256 * HMS_VW_U);
     if (a.n)
         hipLaunchKernelGGL(k_stream_view_groups, dim3((unsigned)(chunks < 2048 ? chunks : 2048)), dim3(256), 0, s, a);
+}
+
+void hm_launch_stream_visit_fold(hipStream_t s, const HmsVisitArgs& a)
+{
+    if (a.n) hipLaunchKernelGGL(k_stream_visit_fold, hms_grid(a.n), dim3(256), 0, s, a);
+}
+
+void hm_launch_stream_visit_emit(hipStream_t s, const HmsVisitArgs& a)
+{
+    const uint64_t chunks = (a.table.mask + 1 + 256 * HMS_VE_U - 1) / (256 * HMS_VE_U);
+    hipLaunchKernelGGL(k_stream_visit_emit, dim3((unsigned)(chunks < 2048 ? chunks : 2048)), dim3(256), 0, s, a);
 }
 
 void hm_launch_stream_raster(hipStream_t s, const HmsRasterArgs& a)

@@ -21,6 +21,7 @@
 #include "hm_stream_frames.h"
 #include "hm_stream_rect.h"
 #include "hm_stream_select.h"
+#include "hm_visit.h"
 
 namespace {
 
@@ -85,6 +86,7 @@ struct hm_stream {
     int64_t rcap = 0;                     /* records rec holds */
     Buf rk, rc, mk, mc;                   /* rollup scratch: relabeled and merged cells */
     Buf tk, tc;                           /* a ranking's HM_TOP_MAX_K records (hm_stream_top*) */
+    Buf vt, vv;                           /* hm_stream_visitors: the per-cell table and its visitors */
     /* several-bucket batches: up to HMS_PAR buckets counted at once, each by
      * its own context, stream and host thread, into its own scratch */
     hm_ctx* pctx[HMS_PAR] = {};
@@ -1006,6 +1008,58 @@ extern "C" int hm_stream_top_groups(hm_stream* s, int64_t hour_lo, int64_t hour_
     return HM_OK;
 }
 
+extern "C" int hm_stream_visitors(hm_stream* s, int64_t hour_lo, int64_t hour_hi, const int64_t* rects, int nrects,
+                                  int64_t min_visitors, uint64_t* keys_out, uint64_t* points_out,
+                                  uint32_t* visitors_out, int64_t capacity, int64_t* n_out, int64_t* withheld_out)
+{
+    if (!n_out || min_visitors < 1 || capacity < 0 || (capacity > 0 && (!keys_out || !points_out))) return HM_E_ARG;
+    /* a per-group view's filter and merge (one label per group, interned once
+     * and reused), then the fold of its (group, cell) records per cell and the
+     * sweep with the threshold */
+    bool empty;
+    int st = stream_view_filter(s, hour_lo, hour_hi, HM_VIEW_EACH, rects, nrects, false, false, &empty);
+    if (st == HM_E_ARG) return st;
+    *n_out = 0;
+    if (withheld_out) withheld_out[0] = withheld_out[1] = 0;
+    if (st || empty) return st;
+    int64_t nd = 0;
+    if ((st = stream_merge(s, &nd)) || nd == 0) return st;
+    hipStream_t q = s->ctx->stream;
+    HmsVisitArgs a;
+    a.keys = (const uint64_t*)s->mk.p;
+    a.counts = (const uint64_t*)s->mc.p;
+    a.n = (uint64_t)nd;
+    a.cb = s->cb;
+    a.zmin = s->zmin;
+    a.zmax = s->zmax;
+    const uint64_t slots = hm_visit_slots((uint64_t)nd);
+    if ((st = stream_buf(s->vt, slots * 16)) || (st = stream_buf(s->vv, slots * 4))) return st;
+    a.table = HmsTable{(uint64_t*)s->vt.p, slots - 1, s->state};
+    a.visitors = (uint32_t*)s->vv.p;
+    a.min_visitors = (uint64_t)min_visitors;
+    a.keys_out = keys_out;
+    a.points_out = points_out;
+    a.visitors_out = visitors_out;
+    a.capacity = (uint64_t)capacity;
+    a.cursor = s->state + HMS_ST_CURSOR;
+    HIPCHK(hipMemsetAsync(s->state + HMS_ST_OVERFLOW, 0, 2 * 8, q));   /* OVERFLOW, CURSOR */
+    HIPCHK(hipMemsetAsync(s->state + HMS_ST_WCELLS, 0, 2 * 8, q));     /* WCELLS, WPOINTS */
+    HIPCHK(hipMemsetAsync(a.visitors, 0, slots * 4, q));
+    hm_launch_stream_init(q, a.table);
+    hm_launch_stream_visit_fold(q, a);
+    hm_launch_stream_visit_emit(q, a);
+    HIPCHK(hipGetLastError());
+    /* the emitted count and the withheld totals, one read-back */
+    if ((st = stream_sync_state(s))) return st;
+    if (s->hstate[HMS_ST_OVERFLOW]) return HM_E_HIP;   /* cannot happen */
+    *n_out = (int64_t)s->hstate[HMS_ST_CURSOR];
+    if (withheld_out) {
+        withheld_out[0] = (int64_t)s->hstate[HMS_ST_WCELLS];
+        withheld_out[1] = (int64_t)s->hstate[HMS_ST_WPOINTS];
+    }
+    return *n_out > capacity ? HM_E_CAPACITY : HM_OK;
+}
+
 /* a raster's tiles, group and log into the kernel's struct: everything but
  * its hours and its grid */
 static void stream_raster_fill(const hm_stream* s, int64_t group, const int64_t* tiles, int ntiles, int bins_log2,
@@ -1424,7 +1478,7 @@ extern "C" int hm_stream_destroy(hm_stream* s)
     if (s->ctx && s->ctx->stream) (void)hipStreamSynchronize(s->ctx->stream);
     for (void* p : {(void*)s->state, (void*)s->bk.keys, (void*)s->bk_alt, (void*)s->bflag, (void*)s->blist,
                     (void*)s->bloc, s->bids.p, s->rec.p, s->plat.p, s->plon.p, s->pkeep.p, s->pstart.p, s->rk.p,
-                    s->rc.p, s->mk.p, s->mc.p, s->tk.p, s->tc.p})
+                    s->rc.p, s->mk.p, s->mc.p, s->tk.p, s->tc.p, s->vt.p, s->vv.p})
         if (p) (void)hipFree(p);
     log_free(s, s->log);
     log_free(s, s->alt);

@@ -70,6 +70,27 @@ __device__ __forceinline__ uint32_t hms_insert(const HmsTable& t, uint64_t k, ui
     return 0;
 }
 
+/* Insert-or-add that returns the key's slot (an index for arrays kept beside
+ * the table), or ~0 when the table is full. */
+__device__ __forceinline__ uint64_t hms_insert_slot(const HmsTable& t, uint64_t k, uint64_t c, uint32_t* overflow)
+{
+    uint64_t h = hms_hash(k) & t.mask;
+    for (uint64_t probe = 0; probe <= t.mask; probe++) {
+        uint64_t cur = t.slots[2 * h];   /* plain read, as hms_insert */
+        if (cur == HMS_EMPTY) {
+            const unsigned long long prev =
+                atomicCAS((unsigned long long*)&t.slots[2 * h], (unsigned long long)HMS_EMPTY, (unsigned long long)k);
+            cur = prev == HMS_EMPTY ? k : prev;
+        }
+        if (cur == k) {
+            atomicAdd((unsigned long long*)&t.slots[2 * h + 1], (unsigned long long)c);
+            return h;
+        }
+        h = (h + 1) & t.mask;
+    }
+    *overflow = 1;
+    return ~0ull;
+}
 
 /* Insert-or-add of a key no other thread of the launch inserts (the stream's
  * batch cells are distinct keys): only the key claim needs an atomic; the

@@ -36,6 +36,13 @@ label is a device rollup of the hour buckets:
                                the busiest cells of one zoom, top_groups /
                                top_users(k, rects, hours) the most active groups
                                there (hm_stream_top_groups)
+  visitors(rects, hours, min_visitors)  per cell of a view its points and its
+                               distinct visitors (groups), only the cells with
+                               at least min_visitors of them (hm_stream_visitors);
+                               top_visited(k, ...) the most visited cells,
+                               tile_visitors(tiles, ...) the visitors as grids,
+                               and tile_raster / tile_images(..., min_users=k)
+                               k-anonymous tiles
   expire(before_hour)         retention: the cells of hours < before_hour
                                leave the stream, their buckets are freed
   forget(users, groups, hours)  erasure: the cells of these users or group
@@ -151,6 +158,63 @@ def _view_records(x: np.ndarray, rects, hours, group) -> np.ndarray:
     if group == "merged":
         rec[:, 0] = ALLGROUPS
     return _sum_records(rec, 4)
+
+
+def _check_min_visitors(min_visitors, what="min_visitors") -> int:
+    """The threshold of a visitors query as an int >= 1.  Pure: no device."""
+    if isinstance(min_visitors, bool) or not isinstance(min_visitors, (int, np.integer)):
+        raise ValueError("%s must be an integer >= 1 (got %r)" % (what, min_visitors))
+    if int(min_visitors) < 1:
+        raise ValueError("%s must be at least 1 (got %d): a cell with no visitor does not exist"
+                         % (what, int(min_visitors)))
+    return int(min_visitors)
+
+
+def _min_users_arg(min_users, user):
+    """tile_raster's / tile_images' min_users: None (no threshold: the plain
+    raster) or the int >= 1 below which a bin is not drawn.  Together with
+    user= it is refused: one user's tile is never k-anonymous.  Pure."""
+    if min_users is None:
+        return None
+    m = _check_min_visitors(min_users, "min_users")
+    if user is not None:
+        raise ValueError("min_users and user=%r exclude each other: one user's tile is never k-anonymous" % (user,))
+    return m
+
+
+def _visitor_records(x: np.ndarray, rects, hours, min_visitors: int) -> np.ndarray:
+    """The out-of-square records x (group, hour or UNDATED_HOUR, zoom, row,
+    col, count) of a visitors query: per distinct cell inside the (unclipped)
+    rectangles and the hours (as _view_records), its points and the number of
+    distinct group ids that own a record of it -- NOGROUP is one id, so the
+    records without a group are one visitor together -- kept when that number
+    reaches min_visitors.  Returns (zoom, row, col, points, visitors)
+    records."""
+    rec = _view_records(x, rects, hours, "each")      # one record per (group, cell)
+    if not len(rec):
+        return np.zeros((0, 5), dtype=np.int64)
+    u, inv = np.unique(rec[:, 1:4], axis=0, return_inverse=True)
+    inv = inv.reshape(-1)
+    pts = np.zeros(len(u), dtype=np.int64)
+    np.add.at(pts, inv, rec[:, 4])
+    vis = np.bincount(inv, minlength=len(u)).astype(np.int64)
+    out = np.concatenate([u, pts[:, None], vis[:, None]], axis=1)
+    return out[vis >= int(min_visitors)]
+
+
+def _haloed_rects(tiles, b: int, h: int):
+    """The rectangle (zoom, row_lo, row_hi, col_lo, col_hi) of each tile's
+    haloed grid: its 2^b x 2^b bins at zoom tz + b and h more on every side,
+    not clipped to the square (a view clips)."""
+    w = (1 << b) + 2 * h
+    return [(tz + b, (tr << b) - h, (tr << b) - h + w, (tc << b) - h, (tc << b) - h + w) for tz, tr, tc in tiles]
+
+
+def _rects_area(rects) -> int:
+    """Cells of the rectangles clipped to the square, overlaps counted twice:
+    an upper bound on the distinct cells a view of them returns."""
+    return sum((min(rhi, 1 << z) - max(rlo, 0)) * (min(chi, 1 << z) - max(clo, 0))
+               for z, rlo, rhi, clo, chi in rects if min(rhi, chi) > 0 and max(rlo, clo) < (1 << z))
 
 
 def tile_rects(tiles, d: int):
@@ -736,8 +800,7 @@ class StreamingHeatmap:
         # merged and one-group views hold at most the rectangles' cells; an
         # 'each' view starts from the last one of these rectangles (one
         # HM_E_CAPACITY retry with the exact size when that is short)
-        area = sum((min(rhi, 1 << z) - max(rlo, 0)) * (min(chi, 1 << z) - max(clo, 0))
-                   for z, rlo, rhi, clo, chi in rects if min(rhi, chi) > 0 and max(rlo, clo) < (1 << z))
+        area = _rects_area(rects)
         mk = ("view", tuple(rects), gw if gw < 0 else 0)
         if gw == _lib.HM_VIEW_EACH:
             cap = max(1024, int(self._query_n.get(mk, min(area, 1 << 20)) * 1.25) + 1024)
@@ -760,6 +823,100 @@ class StreamingHeatmap:
         """Cells of every kept point inside the rectangles (and the hours)."""
         _, z, r, c, cnt = self.view(rects, hours, "merged")
         return device.Counts(z, r, c, cnt, 0, [])
+
+    # ------------------------------------------------------------- visitors
+
+    def visitors_device(self, rects, hours=None, min_visitors=1):
+        """(n, keys, points, visitors, withheld_cells, withheld_points): the
+        distinct cells of view_device(rects, hours) that at least min_visitors
+        different groups produced, as CUDA tensors (int64 keys and points,
+        int32 visitors; the first n entries count, in no particular order),
+        and how many cells and points stayed below the threshold
+        (hm_stream_visitors; out-of-square cells not included).  The records
+        without a group are one visitor together, so visitors is a lower
+        bound on the distinct people."""
+        self.ctx.bind_stream()
+        m = _check_min_visitors(min_visitors)
+        rects, lo, hi, _ = self._view_args(rects, hours, "merged")
+        ra = (ctypes.c_int64 * (5 * len(rects)))(*[v for r in rects for v in r])
+        # at most the rectangles' cells, and usually about as many as the last
+        # such query of this threshold (one HM_E_CAPACITY retry when short)
+        area = _rects_area(rects)
+        mk = ("visitors", tuple(rects), m)
+        cap = max(1024, min(area, int(self._query_n.get(mk, 1 << 20) * 1.25) + 1024))
+        cap = min(max(1024, self._log_capacity()), cap)
+        wh = (ctypes.c_int64 * 2)(0, 0)
+        n, keys, points, vis = self._query(
+            lambda k, c, v, cp, n_out: self.ctx.L.hm_stream_visitors(self.ptr, lo, hi, ra, len(rects), m, k, c, v, cp,
+                                                                     n_out, wh), 1, cap, mk)
+        return n, keys, points, vis, int(wh[0]), int(wh[1])
+
+    def visitors(self, rects, hours=None, min_visitors=1):
+        """Host arrays (zoom, row, col, points, visitors) of the cells inside
+        the rectangles (and hours) with at least min_visitors distinct groups,
+        with the out-of-square side records that lie in the rectangles as given
+        (not clipped, as view's) under the same threshold."""
+        n, keys, points, vis, _, _ = self.visitors_device(rects, hours, min_visitors)
+        z, r, c = device.decode_keys(keys[:n].cpu().numpy().view(np.uint64))
+        out = (z, r, c, points[:n].cpu().numpy(), vis[:n].cpu().numpy().view(np.uint32).astype(np.int64))
+        if not len(self._x):
+            return out
+        # side cells lie outside the square, device cells inside it: the two
+        # sets are disjoint, so each part's visitors are already whole
+        side = _visitor_records(self._x, [tuple(int(v) for v in q) for q in rects], hours, int(min_visitors))
+        return self._with_side(out, side.T)
+
+    def top_visited(self, k, rects, hours=None, min_visitors=1):
+        """[((zoom, row, col), visitors, points)]: the k most visited cells
+        inside the rectangles (and hours) among those with at least
+        min_visitors, in rank order -- visitors descending, then zoom, row,
+        col ascending (hm_cells_top over the keys and visitors of
+        visitors_device).  The out-of-square side records take part."""
+        torch = self._torch
+        k = _top.check_k(k)
+        n, keys, points, vis, _, _ = self.visitors_device(rects, hours, min_visitors)
+        keys, points = keys[:n], points[:n]
+        m, tk, tv = _top.top_cells(keys, vis[:n].to(torch.int64) & 0xFFFFFFFF, k, device=self.device_index)
+        # the chosen cells' points: their keys are distinct, one masked gather
+        chosen = torch.isin(keys, tk) if m else torch.zeros(0, dtype=torch.bool, device=keys.device)
+        ck = keys[chosen].cpu().numpy().view(np.uint64) if m else np.zeros(0, np.uint64)
+        cp = points[chosen].cpu().numpy() if m else np.zeros(0, np.int64)
+        cz, cr, cc = device.decode_keys(ck)
+        pts = {(int(a), int(b), int(d)): int(e) for a, b, d, e in zip(cz, cr, cc, cp)}
+        z, r, c = device.decode_keys(tk.cpu().numpy().view(np.uint64))
+        side = None
+        if len(self._x):
+            rec = _visitor_records(self._x, [tuple(int(v) for v in q) for q in rects], hours, int(min_visitors))
+            side = (rec[:, 0], rec[:, 1], rec[:, 2], rec[:, 4])
+            pts.update({(int(a), int(b), int(d)): int(e) for a, b, d, e in rec[:, :4].tolist()})
+        z, r, c, v = _top.join_ranked(z, r, c, tv.cpu().numpy(), side, k)
+        return [((int(a), int(b), int(d)), int(e), pts[(int(a), int(b), int(d))]) for a, b, d, e in zip(z, r, c, v)]
+
+    def _tile_threshold_raster(self, tiles, hours, bins_log2, halo, min_users, what):
+        """int64 CUDA tensor [T, W, W]: the tiles' grids from the cells with at
+        least min_users visitors -- their points (what = 'points') or their
+        visitors -- through visitors_device over the tiles' haloed rectangles
+        and hm_cells_raster.  HM_VIEW_MAX_RECTS tiles per query, and each
+        query's cells are drawn only into its own tiles' grids: a cell inside
+        the halos of two chunks is in both queries and must not be added
+        twice."""
+        torch = self._torch
+        tiles, _, _, _, b, h = _raster_args(self.zmin, self.zmax, self._index, tiles, hours, None, bins_log2, halo)
+        w = (1 << b) + 2 * h
+        grid = torch.empty((len(tiles), w, w), dtype=torch.int64, device="cuda:%d" % self.device_index)
+        for j in range(0, len(tiles), _lib.HM_VIEW_MAX_RECTS):
+            part = tiles[j:j + _lib.HM_VIEW_MAX_RECTS]
+            n, keys, points, vis, _, _ = self.visitors_device(_haloed_rects(part, b, h), hours, min_users)
+            vals = points[:n] if what == "points" else vis[:n].to(torch.int64) & 0xFFFFFFFF
+            grid[j:j + len(part)] = _raster.raster_cells(keys[:n], vals, part, b, h, device=self.device_index)
+        return grid
+
+    def tile_visitors(self, tiles, hours=None, bins_log2=5, halo=0, min_users=1):
+        """int64 CUDA tensor [T, W, W]: tile_raster's grids holding each bin's
+        distinct visitors instead of its points, bins below min_users left 0
+        (visitors_device, then hm_cells_raster of the keys and visitors)."""
+        return self._tile_threshold_raster(tiles, hours, bins_log2, halo, _check_min_visitors(min_users, "min_users"),
+                                           "visitors")
 
     # ------------------------------------------------------------- rankings
 
@@ -961,14 +1118,22 @@ class StreamingHeatmap:
         """The same rows as a pyarrow Table(id, heatmap JSON)."""
         return _hm.cells_to_table(self.tile_cells(tiles, hours, label, user, max_zoom_level, delta))
 
-    def tile_raster(self, tiles, hours=None, user=None, bins_log2=5, halo=0):
+    def tile_raster(self, tiles, hours=None, user=None, bins_log2=5, halo=0, min_users=None):
         """int64 CUDA tensor [T, W, W], W = 2^bins_log2 + 2 halo: the point
         counts of the tiles [(tz, tr, tc)] as dense grids of zoom tz +
         bins_log2 bins, each with a halo of its neighbours' bins, of hours =
         None (every kept point) or (lo, hi), for every group merged (user =
         None) or the group label `user` (an unknown label: zero grids).
         hm_stream_raster: one filter pass over the log, no merge; the
-        out-of-square side records are never drawn."""
+        out-of-square side records are never drawn.
+
+        min_users = k (>= 1): k-anonymous tiles -- a bin that fewer than k
+        distinct groups produced stays 0 (hm_stream_visitors over the tiles'
+        haloed rectangles, then hm_cells_raster of the emitted cells), so the
+        tile can be published; not together with user=."""
+        m = _min_users_arg(min_users, user)
+        if m is not None:
+            return self._tile_threshold_raster(tiles, hours, bins_log2, halo, m, "points")
         torch = self._torch
         self.ctx.bind_stream()
         tiles, lo, hi, gw, b, h = _raster_args(self.zmin, self.zmax, self._index, tiles, hours, user, bins_log2, halo)
@@ -984,14 +1149,16 @@ class StreamingHeatmap:
             _lib.raise_for(rc)
         return grid
 
-    def tile_images(self, tiles, hours=None, user=None, bins_log2=8, radius=2, scale="log", vmax=None, ramp="heat"):
+    def tile_images(self, tiles, hours=None, user=None, bins_log2=8, radius=2, scale="log", vmax=None, ramp="heat",
+                    min_users=None):
         """uint8 CUDA tensor [T, S, S, 4], S = 2^bins_log2: the tiles as RGBA
         images -- tile_raster with halo = radius, then raster.render (binomial
         blur of `radius`, 'log' or 'linear' levels against vmax, or the
         call's own maximum, coloured through ramp).  raster.png_bytes turns
-        one into a PNG."""
+        one into a PNG.  min_users: tile_raster's, the bins below it are not
+        drawn."""
         _raster.check_render(bins_log2, radius, radius, scale, vmax)
-        grid = self.tile_raster(tiles, hours, user, bins_log2, halo=radius)
+        grid = self.tile_raster(tiles, hours, user, bins_log2, halo=radius, min_users=min_users)
         return _raster.render(grid, bins_log2, radius, radius, scale, vmax, ramp)[0]
 
     def tile_frames(self, tiles, hours, frame_hours=1, user=None, bins_log2=5, halo=0, trailing=None):

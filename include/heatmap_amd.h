@@ -571,6 +571,51 @@ int hm_stream_top(hm_stream* s, int64_t hour_lo, int64_t hour_hi, int64_t group,
 int hm_stream_top_groups(hm_stream* s, int64_t hour_lo, int64_t hour_hi, const int64_t* rects, int nrects,
                          int64_t k, uint32_t* groups_out, uint64_t* counts_out, int64_t* n_out, int64_t* groups_total_out);
 
+/* Visitors: how many different users, not how many points ("unique visitors"
+ * of a place; k-anonymous tiles, where a cell that fewer than k users produced
+ * is not published -- a lone bright pixel is someone's home).  The selection
+ * is hm_stream_view's: the same rectangles, clipped to [0, 2^zoom]^2, a cell
+ * in several rectangles taken once; the hours [hour_lo, hour_hi) clamped
+ * (undated cells are in no range), or the HM_STREAM_ALLTIME pair: everything,
+ * undated cells included.  For each distinct selected cell
+ *   points    the sum of the counts of all its selected records: the count
+ *             hm_stream_view(..., HM_VIEW_MERGED) gives it;
+ *   visitors  the number of distinct group ids 0 .. 0xFFFFFFFE that own at
+ *             least one selected record of it.  A group present in several
+ *             hours of the window counts once, and so does one whose (bucket,
+ *             cell) key repeats in a log not yet compacted.  The records
+ *             without a group (id 0xFFFFFFFE) count together as ONE visitor,
+ *             however many people are behind them, and a group that stands for
+ *             several people is one as well: visitors is a lower bound on the
+ *             distinct people, the safe direction for suppression.
+ * A cell is emitted when visitors >= min_visitors; the others are withheld.
+ *
+ *   hm_stream_visitors  the emitted cells into keys_out (hm_count's layout),
+ *                     points_out and visitors_out (device arrays of `capacity`
+ *                     entries, visitors_out may be NULL), in no particular
+ *                     order; *n_out their number; withheld_out (host int64[2],
+ *                     may be NULL) the cells and the points withheld.
+ *                     HM_E_CAPACITY: *n_out (and withheld_out) are set, the
+ *                     first `capacity` emitted cells are written and nothing at
+ *                     or beyond; capacity = 0 with NULL arrays sizes a call.
+ *                     HM_E_CAPACITY as well when no bucket is left for a
+ *                     group's query label, exactly as a HM_VIEW_EACH view
+ *                     (*n_out = 0 then).  HM_E_ARG, outputs untouched: whatever
+ *                     hm_stream_view refuses, min_visitors < 1, a NULL n_out,
+ *                     NULL key or point arrays with capacity > 0.  An empty
+ *                     selection -- no cell, every rectangle outside the square,
+ *                     the window outside the stream's hours -- is HM_OK with
+ *                     *n_out = 0 and (0, 0) withheld.  The log is left exactly
+ *                     as it is.  On the device: the per-group view's filter
+ *                     and merge, one fold of its distinct (group, cell) records
+ *                     per cell, one sweep that applies the threshold; nothing
+ *                     below it is ever written out.  Waits for the merge's
+ *                     read-back and, behind the sweep, for the numbers it
+ *                     returns. */
+int hm_stream_visitors(hm_stream* s, int64_t hour_lo, int64_t hour_hi, const int64_t* rects, int nrects,
+                       int64_t min_visitors, uint64_t* keys_out, uint64_t* points_out, uint32_t* visitors_out,
+                       int64_t capacity, int64_t* n_out, int64_t* withheld_out);
+
 /* Multi-GPU exchange of hm_count cells (one process per GPU; the collectives
  * are RCCL calls made by the caller, heatmap_amd/multigpu.py).  They replace
  * the reference's two shuffles, reduceByKey (heatmap.py:111) and groupByKey

@@ -118,6 +118,27 @@ ranges overlap; for the two cell rankings also the selection alone
 hm_stream_view and hm_stream_import is needed, so a checkout of the parent
 commit can run it); --parent-json FILE puts that run's times into this one's
 result as "parent_sort_ms".
+
+    python tools/bench_stream.py --retain 24 --batches 30 --warmup 0 --visitors --out profiles/stream_visitors.json
+
+--retain H --visitors: distinct visitors on the steady retained log, on the
+same cells imported with group = a hash of the cell % 1000 (--top's groups):
+the cells with at least 5 visitors in the trailing 24 hours, their points and
+visitors and the withheld totals (visitors_device(min_visitors=5); those groups
+are a function of the cell, so every cell has one visitor and all of it is
+withheld: min_visitors=1, where all of it is emitted, is timed beside it),
+against the
+route a caller had before it -- view_device(rects, hours, 'each'), one record
+per (group, cell), then a device torch.unique(return_inverse, return_counts)
+over the keys, a scatter_add of the points, the mask and the gathers -- for
+--top's two selections: the whole of zoom 14 and the 4 x 3-tile screen at the
+detail zoom.  Both routes are warmed, then take VISITORS_REPS alternating
+repetitions; host ms around each, which ends in a synchronise; median and
+min-max of each, "not distinguishable" when the ranges overlap, and the two
+results compared record by record.  --each-only times the earlier route alone
+(nothing newer than hm_stream_view and hm_stream_import is needed, so a
+checkout of the parent commit can run it); --parent-json FILE puts that run's
+times into this one's result as "parent_each_unique_ms".
 """
 import argparse
 import json
@@ -671,31 +692,39 @@ def _two_key_top(keys, counts, k):
     return ks[j][:k], cs[:k]
 
 
+def _hot_screen(s, a, h24):
+    """the 4 x 3 tiles of 256 x 256 detail-zoom cells around the heaviest cell of the hours h24"""
+    n, keys, counts, _ = s.window_device(*h24)
+    k18 = keys[:n][(keys[:n] >> 58) == a.zmax]
+    c18 = counts[:n][(keys[:n] >> 58) == a.zmax]
+    heavy = int(k18[torch.argmax(c18)].item())
+    r, c = (heavy >> 29) & 0x1FFFFFFF, heavy & 0x1FFFFFFF
+    tr, tc = (r >> 8) - 1, (c >> 8) - 1
+    return [(a.zmax, (tr + i) << 8, (tr + i + 1) << 8, (tc + j) << 8, (tc + j + 1) << 8)
+            for i in range(3) for j in range(4)]
+
+
+def _grouped_copy(s, a):
+    """the log's cells under group = a hash of the cell % 1000, in a stream of their own"""
+    ne, ek, ec, eg, eh = s.export_device()
+    g1000 = ((ek[:ne] ^ (ek[:ne] >> 23)) * 2654435761 % 1000).to(torch.int32)
+    g = StreamingHeatmap(a.zmin, a.zmax, base_hour=BASE, initial_cells=max(1024, ne))
+    rc = s.ctx.L.hm_stream_import(g.ptr, ek.data_ptr(), ec.data_ptr(), g1000.data_ptr(), eh.data_ptr(), ne, 1)
+    assert rc == 0, rc
+    return g
+
+
 def top_bench(s, a, lo, hi):
     """--top / --sort-only (module docstring) on the stream as it stands"""
     import ctypes
 
     L = s.ctx.L
     h24 = (max(lo, hi - 24), hi)
-    n, keys, counts, _ = s.window_device(*h24)
-    k18 = keys[:n][(keys[:n] >> 58) == a.zmax]
-    c18 = counts[:n][(keys[:n] >> 58) == a.zmax]
-    heavy = int(k18[torch.argmax(c18)].item())
-    del keys, counts, k18, c18
-    r, c = (heavy >> 29) & 0x1FFFFFFF, heavy & 0x1FFFFFFF
-    tr, tc = (r >> 8) - 1, (c >> 8) - 1
-    screen = [(a.zmax, (tr + i) << 8, (tr + i + 1) << 8, (tc + j) << 8, (tc + j + 1) << 8)
-              for i in range(3) for j in range(4)]
+    screen = _hot_screen(s, a, h24)
     zw = min(14, a.zmax)
     out = {"hours": list(h24), "reps": TOP_REPS, "log_cells": s.cells()[0],
            "timing": "host ms around the route plus one synchronise; both routes warmed, then alternating"}
-    # the groups: the log's cells under group = a hash of the cell % 1000, in a stream of their own
-    ne, ek, ec, eg, eh = s.export_device()
-    g1000 = ((ek[:ne] ^ (ek[:ne] >> 23)) * 2654435761 % 1000).to(torch.int32)
-    g = StreamingHeatmap(a.zmin, a.zmax, base_hour=BASE, initial_cells=max(1024, ne))
-    rc = L.hm_stream_import(g.ptr, ek.data_ptr(), ec.data_ptr(), g1000.data_ptr(), eh.data_ptr(), ne, 1)
-    assert rc == 0, rc
-    del ek, ec, eg, eh
+    g = _grouped_copy(s, a)
 
     def sort_cells(rects, k):
         nv, vk, vc, _ = s.view_device(rects, h24)
@@ -785,6 +814,82 @@ def top_bench(s, a, lo, hi):
     return out
 
 
+VISITORS_REPS = 25
+VISITORS_MIN = (5, 1)     # the k-anonymity threshold measured, and 1: every cell emitted
+
+
+def visitors_bench(s, a, lo, hi):
+    """--visitors / --each-only (module docstring) on the stream as it stands"""
+    h24 = (max(lo, hi - 24), hi)
+    screen = _hot_screen(s, a, h24)
+    zw = min(14, a.zmax)
+    out = {"hours": list(h24), "reps": VISITORS_REPS, "log_cells": s.cells()[0],
+           "groups": "1000, group = a hash of the cell: every cell belongs to one group, so min_visitors = 5 "
+                     "withholds all of it and min_visitors = 1 emits all of it",
+           "timing": "host ms around the route plus one synchronise; both routes warmed, then alternating"}
+    g = _grouped_copy(s, a)
+
+    def each_route(rects, m):
+        """the route before hm_stream_visitors: one record per (group, cell), then unique, mask and gathers"""
+        nv, vk, vc, _ = g.view_device(rects, h24, "each")
+        cells, inv, vis = torch.unique(vk[:nv], return_inverse=True, return_counts=True)
+        pts = torch.zeros(cells.numel(), dtype=torch.int64, device="cuda").scatter_add_(0, inv, vc[:nv])
+        keep = vis >= m
+        return nv, cells[keep], pts[keep], vis[keep], int((~keep).sum().item()), int(pts[~keep].sum().item())
+
+    def visitors_route(rects, m):
+        n, vk, vp, vv, wc, wp = g.visitors_device(rects, h24, m)
+        return n, vk[:n], vp[:n], vv[:n].to(torch.int64) & 0xFFFFFFFF, wc, wp
+
+    cases = [("%s_min%d" % (name, m), rects, m)
+             for name, rects in (("a_whole_z%d" % zw, [(zw, 0, 1 << zw, 0, 1 << zw)]),
+                                 ("b_screen_4x3_tiles_z%d" % a.zmax, screen)) for m in VISITORS_MIN]
+    ok = True
+    for name, rects, m in cases:
+        routes = [("each_unique_ms", each_route)] + ([] if a.each_only else [("visitors_ms", visitors_route)])
+        t = {key: [] for key, _ in routes}
+        last = {}
+        for key, f in routes:
+            f(rects, m)                       # warm: code objects, the capacity memo, the scratch, the labels
+            f(rects, m)
+        for _ in range(VISITORS_REPS):
+            for key, f in routes:
+                ms, last[key] = _ms(lambda: f(rects, m))
+                t[key].append(ms)
+        e = last["each_unique_ms"]
+        res = {"rects": [list(map(int, q)) for q in rects], "min_visitors": m, "group_cell_records": int(e[0]),
+               "emitted": int(e[1].numel()), "withheld_cells": e[4], "withheld_points": e[5]}
+        for key in t:
+            res[key] = _stats(t[key])
+        if not a.each_only:
+            v = last["visitors_ms"]
+            order = torch.argsort(v[1])       # the call's order is unspecified; unique's is by key
+            same = v[0] == e[1].numel() and v[4:] == e[4:] and \
+                all(torch.equal(x[order], y) for x, y in zip(v[1:4], e[1:4]))
+            ok &= bool(same)
+            res["visitors_equals_each_route"] = bool(same)
+            o, w = res["each_unique_ms"], res["visitors_ms"]
+            res["verdict"] = ("not distinguishable" if w["min"] <= o["max"] and o["min"] <= w["max"] else
+                              "visitors faster" if w["median"] < o["median"] else "visitors slower")
+        out[name] = res
+    g.close()
+    if not a.each_only:
+        out["check"] = "ok" if ok else "FAIL"
+    if a.parent_json:
+        pj = json.load(open(a.parent_json))["visitors"]
+        assert pj["log_cells"] == out["log_cells"] and pj["hours"] == out["hours"]
+        for name, *_ in cases:
+            assert pj[name]["emitted"] == out[name]["emitted"]
+            out[name]["parent_each_unique_ms"] = pj[name]["each_unique_ms"]
+            o, w = pj[name]["each_unique_ms"], out[name]["visitors_ms"]
+            out[name]["verdict_vs_parent"] = ("not distinguishable" if w["min"] <= o["max"] and o["min"] <= w["max"]
+                                              else "visitors faster" if w["median"] < o["median"] else
+                                              "visitors slower")
+        out["parent_note"] = ("this script with --visitors --each-only run by a checkout of the parent commit (its "
+                              "library and package) on the same seeded log, in the same session")
+    return out
+
+
 def retain(a):
     """--retain H: a stream under retention (module docstring)"""
     n, H = int(a.batch), a.retain
@@ -819,6 +924,7 @@ def retain(a):
     fra = frames_bench(s, a, BASE + total) if a.frames else None
     fgt = forget_bench(s, a, BASE + total - 1 - H, BASE + total) if a.forget or a.expire_only else None
     top = top_bench(s, a, BASE + total - 1 - H, BASE + total) if a.top or a.sort_only else None
+    vis = visitors_bench(s, a, BASE + total - 1 - H, BASE + total) if a.visitors or a.each_only else None
     result = json.dumps({
         "metric": "stream under retention: expire(newest - H) and window(newest - H, newest + 1) per one-hour batch",
         "retain_hours": H, "batch_points": n, "batches": a.batches, "warmup": a.warmup, "zooms": [a.zmin, a.zmax],
@@ -837,6 +943,7 @@ def retain(a):
         "frames": fra,
         "forget": fgt,
         "top": top,
+        "visitors": vis,
         "series": series,
         "data": "synthetic (heatmap_amd.synth, generated on device, resident in HBM)"})
     print(result)
@@ -880,6 +987,10 @@ def main():
                     help="with --retain 24 or more: the 100 hottest cells and the 10 most active groups against a view "
                          "and a device sort (module docstring)")
     ap.add_argument("--sort-only", action="store_true", help="with --retain: --top's view-and-sort routes alone")
+    ap.add_argument("--visitors", action="store_true",
+                    help="with --retain 24 or more: the cells with at least 5 distinct visitors (hm_stream_visitors) "
+                         "against a per-group view, a device unique and a mask (module docstring)")
+    ap.add_argument("--each-only", action="store_true", help="with --retain: --visitors' view-and-unique route alone")
     ap.add_argument("--readd-only", action="store_true",
                     help="with --retain: time only the re-adding of the retained batches to a fresh stream")
     ap.add_argument("--parent-json", default=None, metavar="FILE",
@@ -887,7 +998,8 @@ def main():
                          "--snapshot: its --readd-only result, kept as parent_readd_ms; with --raster: its "
                          "--view-only result, kept as parent_view_ms; with --frames: its --loop-only result, kept as "
                          "parent_loop_ms; with --forget: its --expire-only result, kept as parent_expire_ms; with "
-                         "--top: its --sort-only result, kept as parent_sort_ms")
+                         "--top: its --sort-only result, kept as parent_sort_ms; with --visitors: its --each-only result, kept as "
+                         "parent_each_unique_ms")
     ap.add_argument("--out", default=None, metavar="FILE", help="with --retain: also write the JSON line to FILE")
     a = ap.parse_args()
     if a.retain > 0:
