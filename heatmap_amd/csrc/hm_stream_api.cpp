@@ -324,8 +324,11 @@ static void stream_appended(hm_stream* s, uint64_t m, const uint32_t* buckets, u
          * log stays compact when it was empty, or when none of the buckets
          * has cells in it yet (the log's buckets all known) */
         if (s->llen == 0) s->log_buckets.clear();
+        /* (cells not told apart may be of any bucket, one with cells in the
+         * log included: they are fresh only for an empty log) */
         bool fresh = !s->log_buckets.count(HMS_ANY_BUCKET);
-        for (uint32_t j = 0; j < nb && fresh; j++) fresh = !s->log_buckets.count(buckets[j]);
+        for (uint32_t j = 0; j < nb && fresh; j++)
+            fresh = buckets[j] != HMS_ANY_BUCKET && !s->log_buckets.count(buckets[j]);
         s->compact = s->compact && (s->llen == 0 || fresh);
         for (uint32_t j = 0; j < nb; j++) s->log_buckets.insert(buckets[j]);
     }
