@@ -37,6 +37,8 @@ HM_RASTER_MAX_FRAMES = 1 << 16   # hm_stream_raster_frames
 HM_SELECT_MAX_GROUPS = 1 << 20   # hm_stream_forget / hm_stream_export_select
 HM_SCALE_LINEAR, HM_SCALE_LOG = 0, 1
 HM_TOP_MAX_K = 4096              # hm_cells_top / hm_stream_top / hm_stream_top_groups
+HM_REGION_MAX_REGIONS, HM_REGION_MAX_SPANS, HM_REGION_MAX_ROWS = 4096, 1 << 20, 1 << 20   # hm_stream_region_*
+HM_REGION_MAX_TOTALS = 1 << 22   # frames * regions of one hm_stream_region_series
 
 EXPORTS = ["hm_abi_version", "hm_status_string", "hm_ctx_create", "hm_ctx_set_stream", "hm_ctx_destroy", "hm_ctx_tune",
            "hm_project", "hm_project_scalar", "hm_count", "hm_count_tiles", "hm_count_grouped", "hm_count_grouped_tiles",
@@ -46,8 +48,19 @@ EXPORTS = ["hm_abi_version", "hm_status_string", "hm_ctx_create", "hm_ctx_set_st
            "hm_stream_destroy", "hm_stream_raster", "hm_cells_raster", "hm_raster_render",
            "hm_stream_raster_frames", "hm_raster_accumulate", "hm_stream_forget", "hm_stream_export_select",
            "hm_cells_top", "hm_stream_top", "hm_stream_top_groups", "hm_stream_visitors",
+           "hm_stream_region_series", "hm_stream_region_view", "hm_stream_region_visitors",
            "hm_dense_grid_size", "hm_cells_route", "hm_cells_merge", "hm_cells_merge_runs",
            "hm_cells_route_pieces", "hm_cells_merge_pieces", "hm_dense_cells", "hm_format_bins", "hm_format_ids", "hm_bench_read"]
+
+
+
+class hm_regions(ctypes.Structure):
+    """The region table of hm_stream_region_* (host arrays of uint32)."""
+    _fields_ = [("zoom", ctypes.c_int), ("row_lo", ctypes.c_int64), ("nrows", ctypes.c_int64),
+                ("nspans", ctypes.c_int64), ("nregions", ctypes.c_int64),
+                ("row_ptr", ctypes.POINTER(ctypes.c_uint32)), ("col_lo", ctypes.POINTER(ctypes.c_uint32)),
+                ("col_hi", ctypes.POINTER(ctypes.c_uint32)), ("region", ctypes.POINTER(ctypes.c_uint32))]
+
 
 _LIB = None
 _LOCK = threading.Lock()
@@ -144,6 +157,11 @@ def load() -> ctypes.CDLL:
                                            P(c.c_int64), P(c.c_int64)]
         L.hm_stream_visitors.argtypes = [vp, c.c_int64, c.c_int64, P(c.c_int64), c.c_int, c.c_int64, vp, vp, vp,
                                          c.c_int64, P(c.c_int64), P(c.c_int64)]
+        L.hm_stream_region_series.argtypes = [vp, c.c_int64, c.c_int64, c.c_int64, c.c_int64, P(hm_regions), vp]
+        L.hm_stream_region_view.argtypes = [vp, c.c_int64, c.c_int64, c.c_int64, P(hm_regions), vp, vp, vp, c.c_int64,
+                                            P(c.c_int64)]
+        L.hm_stream_region_visitors.argtypes = [vp, c.c_int64, c.c_int64, P(hm_regions), c.c_int64, vp, vp,
+                                                P(c.c_int64)]
         L.hm_dense_grid_size.argtypes = [c.c_int]
         L.hm_dense_grid_size.restype = c.c_int64
         L.hm_cells_route.argtypes = [vp, vp, vp, c.c_int64, c.c_int, c.c_int, c.c_int, vp, vp, vp, c.c_int,

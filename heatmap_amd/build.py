@@ -18,7 +18,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "_lib")
 LIB = os.path.join(LIBDIR, "libheatmap_amd.so")
-SOURCES = ["hm_kernels.hip", "hm_aggregate.hip", "hm_general.hip", "hm_stream.hip", "hm_merge.hip", "hm_raster.hip",
+SOURCES = ["hm_kernels.hip", "hm_aggregate.hip", "hm_general.hip", "hm_stream.hip", "hm_stream_region.hip", "hm_merge.hip", "hm_raster.hip",
            "hm_top.hip", "hm_api.cpp", "hm_stream_api.cpp", "hm_host.c"]
 ARCH = os.environ.get("HM_OFFLOAD_ARCH", "gfx950")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "--offload-arch=" + ARCH,

@@ -572,7 +572,9 @@ enum {
     HMS_ST_OCCUPIED = 0, HMS_ST_OVERFLOW = 1, HMS_ST_CURSOR = 2, HMS_ST_BUCKETS = 3, HMS_ST_BFULL = 4,
     HMS_ST_EXOTIC = 5, HMS_ST_BMM = 6 /* a bucket of the batch (the only one if NLIST == 1) */, HMS_ST_NLIST = 7,
     HMS_ST_ERR = 8 /* first bad hour: index << 8 | HM_E_RANGE */,
-    HMS_ST_WCELLS = 9, HMS_ST_WPOINTS = 10 /* hm_stream_visitors: the cells and points withheld */, HMS_ST_COUNT = 16
+    HMS_ST_WCELLS = 9, HMS_ST_WPOINTS = 10 /* hm_stream_visitors: the cells and points withheld */,
+    HMS_ST_PAIRS = 11 /* hm_stream_region_visitors: the (survivor, covering span) pairs of the filter pass */,
+    HMS_ST_COUNT = 16
 };
 #define HMS_MAX_PARTS 64                 /* batches of more buckets take the grouped general path */
 #define HMS_NOGROUP 0xFFFFFFFEu          /* kept points without a user group */
@@ -876,6 +878,59 @@ struct HmsVisitArgs {
 void hm_launch_stream_visit_fold(hipStream_t s, const HmsVisitArgs& a);
 /* the sweep: emitted cells out, state[HMS_ST_WCELLS / HMS_ST_WPOINTS] += the withheld */
 void hm_launch_stream_visit_emit(hipStream_t s, const HmsVisitArgs& a);
+/* A region query (hm_stream_region_*, hm_region.h, hm_stream_region.hip): the
+ * log's cells of ONE zoom that a span of the region set covers, of the wanted
+ * hours and group(s).  k_stream_view's pass with the rectangle loop replaced
+ * by a lookup in the row's spans, and one of three sinks:
+ *   totals   totals[frame][region] += count for every (survivor, covering
+ *            span); the frames are k_stream_raster_frames' (alltime: one).
+ *            With at most HMS_RG_TOT_LDS accumulators a block sums into a table
+ *            of its own in LDS and adds it to the global one once, when it
+ *            ends; with more, equal accumulators are summed across a wave row
+ *            (HMS_RG_TURNS of them, the rest go alone) before the global add.
+ *   cells    a survivor that any span covers is written once, re-keyed to the
+ *            view's label as k_stream_view writes it.
+ *   records  (region << 32 | group, count) for every (survivor, covering
+ *            span), summed per block in an LDS table of HMS_RG_REC_SLOTS slots
+ *            that is written out when the block ends; a record that finds no
+ *            slot within HMS_RG_REC_PROBES is written as it is.  The first
+ *            `capacity` records are written, *cursor counts them all.
+ * The table (row_ptr, col_lo, col_hi, region: device words) is staged in LDS
+ * once per block when it has at most HMS_RG_STAGE_WORDS words. */
+#define HMS_RG_STAGE_WORDS 6144          /* nrows + 1 + 3 nspans: 24 KB of a block's LDS */
+#define HMS_RG_TOT_LDS 2048              /* frames x regions a block accumulates in LDS (16 KB) */
+#define HMS_RG_TURNS 4
+#define HMS_RG_REC_SLOTS 1024            /* 16 KB */
+#define HMS_RG_REC_PROBES 8
+enum { HMS_RG_SINK_TOTALS = 0, HMS_RG_SINK_CELLS = 1, HMS_RG_SINK_RECORDS = 2 };
+struct HmsRegionArgs {
+    HmsViewArgs v;           /* the log, hours, group, outputs, cursor and state as a view's; no rectangle */
+    int z;                   /* the regions' zoom */
+    int stage;               /* the table goes to LDS */
+    uint64_t id_lo, id_span; /* the id interval of the covered rows (hms_region_ids) */
+    uint32_t nrows, nspans, nregions;
+    const uint32_t* row_ptr; /* device: nrows + 1 */
+    const uint32_t* col_lo;  /* device: nspans each */
+    const uint32_t* col_hi;
+    const uint32_t* region;
+    /* totals: accumulator (frame - first clamped hour's frame) * nregions + region of `totals`, below ntot */
+    unsigned long long* totals;
+    uint32_t ntot;
+    uint32_t fh, phase;      /* hm_stream_frames.h; alltime: not read, every survivor is in frame 0 */
+    uint64_t capacity;       /* records: what keys_out / counts_out hold */
+};
+void hm_launch_stream_region(hipStream_t s, const HmsRegionArgs& a, int sink);
+/* the blocks of that launch over a log of n cells (each writes one records table at most) */
+uint32_t hm_stream_region_blocks(uint64_t n);
+/* distinct (region << 32 | group, count) records folded per region: points[r]
+ * += count, visitors[r] += 1 (both zeroed by the caller), each block through
+ * arrays of its own in LDS */
+void hm_launch_region_visit_fold(hipStream_t s, const uint64_t* keys, const uint64_t* counts, uint64_t n,
+                                 uint32_t nregions, uint64_t* points, uint32_t* visitors);
+/* the threshold: a region with 1 <= visitors < min_visitors gets 0 and 0, and
+ * state[HMS_ST_WCELLS / HMS_ST_WPOINTS] += 1 and its points */
+void hm_launch_region_visit_sweep(hipStream_t s, uint32_t nregions, uint64_t min_visitors, uint64_t* points,
+                                  uint32_t* visitors, unsigned long long* state);
 /* the occupied slots of a bucket table -> list, their number added to *n */
 void hm_launch_stream_occupied(hipStream_t s, const HmsBuckets& b, uint32_t* list, unsigned long long* n);
 

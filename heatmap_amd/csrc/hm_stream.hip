@@ -60,6 +60,7 @@
 #include "hm_device.h"
 #include "hm_pipeline.h"
 #include "hm_table.h"
+#include "hm_stream_dev.h"
 #define HMS_SELECT_FN __device__ __forceinline__   /* hms_select_has on the device */
 #include "hm_stream_select.h"
 #define HM_VISIT_FN __device__ __forceinline__   /* hm_visit_judge on the device */
@@ -81,29 +82,6 @@ __device__ __forceinline__ uint64_t hms_cell_key(uint64_t id, int zmin, int zmax
     while (z < zmax && id >= hms_pyr_off(z + 1)) z++;
     const uint64_t m = id - hms_pyr_off(z);
     return ((uint64_t)z << 58) | ((m >> z) << 29) | (m & ((1ull << z) - 1ull));
-}
-
-/* bucket id of key k (interning it), or HMS_NO_BUCKET when the table is full */
-__device__ __forceinline__ uint32_t hms_intern(const HmsBuckets& b, uint64_t k, uint32_t* claimed)
-{
-    uint64_t h = hms_hash(k) & b.mask;
-    for (uint64_t probe = 0; probe <= b.mask; probe++) {
-        /* a plain (L1-cacheable) read: a key word changes once, EMPTY -> key,
-         * so a stale EMPTY only sends us to the CAS, which returns the truth */
-        uint64_t cur = b.keys[h];
-        if (cur == HMS_EMPTY) {
-            const unsigned long long prev =
-                atomicCAS((unsigned long long*)&b.keys[h], (unsigned long long)HMS_EMPTY, (unsigned long long)k);
-            if (prev == HMS_EMPTY) {
-                *claimed += 1;
-                return (uint32_t)h;
-            }
-            cur = prev;
-        }
-        if (cur == k) return (uint32_t)h;
-        h = (h + 1) & b.mask;
-    }
-    return HMS_NO_BUCKET;
 }
 
 /* a bucket met by a wave: flagged with the batch epoch (a plain store -- the
@@ -531,18 +509,6 @@ __global__ __launch_bounds__(256) void k_stream_export(HmsEmitArgs a)
             if (a.periods_out) a.periods_out[i] = pw == HMS_UNDATED ? HM_STREAM_UNDATED : a.base + pw;
         }
     }
-}
-
-/* label key of a raw bucket key in a view (the window's or alltime's label,
- * under the group, HMS_ALLGROUPS or the selected group), or ~0: not in it */
-__device__ __forceinline__ uint64_t hms_view_key(const HmsViewArgs& a, uint64_t bk)
-{
-    const uint32_t pw = (uint32_t)bk, g = (uint32_t)(bk >> 32);
-    const bool dated = (pw >> 28) == 0;
-    const bool in = a.alltime ? (dated || pw == HMS_UNDATED) : (dated && pw >= a.lo && pw < a.hi);
-    if (!in || (a.gmode == HMS_VIEW_GROUP && g != a.group)) return ~0ull;
-    const uint32_t lp = (a.alltime ? HMS_TYPE_ALLTIME : HMS_TYPE_WINDOW) << 28;
-    return ((uint64_t)(a.gmode == HMS_VIEW_MERGED ? HMS_ALLGROUPS : g) << 32) | lp;
 }
 
 /* A viewport query's filter: ONE pass over the log's keys.  A thread takes

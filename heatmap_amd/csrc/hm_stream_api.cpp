@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "hm_ctx.h"
+#include "hm_region.h"
 #include "hm_stream_frames.h"
 #include "hm_stream_rect.h"
 #include "hm_stream_select.h"
@@ -87,6 +88,13 @@ struct hm_stream {
     Buf rk, rc, mk, mc;                   /* rollup scratch: relabeled and merged cells */
     Buf tk, tc;                           /* a ranking's HM_TOP_MAX_K records (hm_stream_top*) */
     Buf vt, vv;                           /* hm_stream_visitors: the per-cell table and its visitors */
+    /* hm_stream_region_*: the call's span table on the device, and the pinned
+     * words it is packed into for the upload (gev: that upload is done, the
+     * words may be overwritten) */
+    Buf gt;
+    uint32_t* ghost = nullptr;
+    size_t ghost_words = 0;
+    hipEvent_t gev = nullptr;
     /* several-bucket batches: up to HMS_PAR buckets counted at once, each by
      * its own context, stream and host thread, into its own scratch */
     hm_ctx* pctx[HMS_PAR] = {};
@@ -1063,6 +1071,200 @@ extern "C" int hm_stream_visitors(hm_stream* s, int64_t hour_lo, int64_t hour_hi
     return *n_out > capacity ? HM_E_CAPACITY : HM_OK;
 }
 
+/* ---- region queries: the view's selection with a span table in place of
+ * the rectangles (hm_region.h; kernels in hm_stream_region.hip) ---- */
+
+/* A region query's table: checked on the host (hms_region_check), so that the
+ * kernel never indexes outside it, then packed into the stream's pinned words
+ * and uploaded into the stream's scratch; a's table fields filled in.  A
+ * refused table is HM_E_ARG with the offending span or row as hm_last_error's
+ * index.  A table without spans is not uploaded: it selects nothing. */
+static int stream_region_table(hm_stream* s, const hm_regions* rg, HmsRegionArgs& a)
+{
+    hm_ctx* ctx = s->ctx;
+    const int64_t nr = std::min<int64_t>(std::max<int64_t>(rg->nregions, 1), HM_REGION_MAX_REGIONS);
+    std::vector<uint32_t> scratch(2 * (size_t)nr);
+    int64_t bad = 0;
+    if (hms_region_check(rg->zoom, rg->row_lo, rg->nrows, rg->nspans, rg->nregions, rg->row_ptr, rg->col_lo,
+                         rg->col_hi, rg->region, s->zmin, s->zmax, scratch.data(), &bad) != HMS_RG_OK) {
+        ctx->last_err_index = bad;
+        ctx->last_err_kind = HM_E_ARG;
+        return HM_E_ARG;
+    }
+    const HmsRegionIds ids = hms_region_ids(rg->zoom, rg->row_lo, rg->nrows);
+    a.z = rg->zoom;
+    a.id_lo = ids.id_lo;
+    a.id_span = ids.span;
+    a.nrows = (uint32_t)rg->nrows;
+    a.nspans = (uint32_t)rg->nspans;
+    a.nregions = (uint32_t)rg->nregions;
+    a.row_ptr = a.col_lo = a.col_hi = a.region = nullptr;
+    a.stage = 0;
+    a.totals = nullptr;
+    a.ntot = 0;
+    a.fh = 1, a.phase = 0;
+    a.capacity = 0;
+    a.v.nrects = 0;
+    a.v.box_lo = a.v.box_span = 0;
+    if (rg->nspans == 0) return HM_OK;
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t nrp = (size_t)rg->nrows + 1, ns = (size_t)rg->nspans, words = nrp + 3 * ns;
+    if (!s->gev) HIPCHK(hipEventCreateWithFlags(&s->gev, hipEventDisableTiming));
+    HIPCHK(hipEventSynchronize(s->gev));   /* the last call's upload has left the pinned words */
+    if (s->ghost_words < words) {
+        if (s->ghost) HIPCHK(hipHostFree(s->ghost));
+        s->ghost = nullptr;
+        s->ghost_words = 0;
+        if (hipHostMalloc((void**)&s->ghost, words * 4) != hipSuccess) {
+            (void)hipGetLastError();
+            return HM_E_NOMEM;
+        }
+        s->ghost_words = words;
+    }
+    std::copy(rg->row_ptr, rg->row_ptr + nrp, s->ghost);
+    std::copy(rg->col_lo, rg->col_lo + ns, s->ghost + nrp);
+    std::copy(rg->col_hi, rg->col_hi + ns, s->ghost + nrp + ns);
+    std::copy(rg->region, rg->region + ns, s->ghost + nrp + 2 * ns);
+    int st;
+    if ((st = stream_buf(s->gt, words * 4))) return st;
+    HIPCHK(hipMemcpyAsync(s->gt.p, s->ghost, words * 4, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipEventRecord(s->gev, ctx->stream));
+    a.row_ptr = (const uint32_t*)s->gt.p;
+    a.col_lo = a.row_ptr + nrp;
+    a.col_hi = a.col_lo + ns;
+    a.region = a.col_hi + ns;
+    a.stage = words <= HMS_RG_STAGE_WORDS;
+    return HM_OK;
+}
+
+/* the hours and the group of a region query, as a view's */
+static void stream_region_select(HmsRegionArgs& a, const HourWindow& w, int64_t group)
+{
+    a.v.alltime = w.kind == HW_ALLTIME;
+    a.v.lo = w.lo, a.v.hi = w.hi;
+    a.v.gmode = group == HM_VIEW_MERGED ? HMS_VIEW_MERGED : (group == HM_VIEW_EACH ? HMS_VIEW_EACH : HMS_VIEW_GROUP);
+    a.v.group = group >= 0 ? (uint32_t)group : 0u;
+}
+
+extern "C" int hm_stream_region_series(hm_stream* s, int64_t hour_lo, int64_t hour_hi, int64_t frame_hours,
+                                       int64_t group, const hm_regions* regions, uint64_t* totals_out)
+{
+    if (!s || !regions || !totals_out || group < HM_VIEW_MERGED || group > (int64_t)HMS_NOGROUP) return HM_E_ARG;
+    const bool alltime = hour_lo == HM_STREAM_ALLTIME && hour_hi == HM_STREAM_ALLTIME;
+    HmsRegionArgs a;
+    int st;
+    if ((st = stream_region_table(s, regions, a))) return st;
+    HmsFramePlan p;
+    p.nframes = 1, p.frame0 = 0, p.lo = 0, p.hi = 1, p.fh = 1, p.phase = 0;
+    if (!alltime && hms_frame_plan((int64_t)s->base, hour_lo, hour_hi, frame_hours,
+                                   HM_REGION_MAX_TOTALS / (int64_t)a.nregions, &p))
+        return HM_E_ARG;
+    hm_ctx* ctx = s->ctx;
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t q = ctx->stream;
+    HIPCHK(hipMemsetAsync(totals_out, 0, (size_t)p.nframes * a.nregions * 8, q));
+    if (a.nspans == 0 || s->llen == 0 || p.lo == p.hi) return HM_OK;   /* nothing selected: zeros */
+    a.v.keys = s->log.keys.p;
+    a.v.counts = s->log.counts.p;
+    a.v.n = s->llen;
+    a.v.buckets = s->bk;
+    a.v.cb = s->cb;
+    a.v.keys_out = a.v.counts_out = nullptr;
+    a.v.cursor = nullptr;
+    a.v.state = s->state;
+    stream_region_select(a, HourWindow{alltime ? HW_ALLTIME : HW_RANGE, p.lo, p.hi}, group);
+    /* the frames the clamped hours reach, counted from the first one's */
+    int64_t nfl = alltime ? 1 : (int64_t)((p.hi - 1 - p.lo + p.phase) / p.fh) + 1;
+    nfl = std::min<int64_t>(nfl, p.nframes - p.frame0);
+    a.totals = (unsigned long long*)totals_out + (uint64_t)p.frame0 * a.nregions;
+    a.ntot = (uint32_t)(nfl * a.nregions);
+    a.fh = p.fh, a.phase = p.phase;
+    hm_launch_stream_region(q, a, HMS_RG_SINK_TOTALS);
+    HIPCHK(hipGetLastError());
+    return HM_OK;
+}
+
+extern "C" int hm_stream_region_view(hm_stream* s, int64_t hour_lo, int64_t hour_hi, int64_t group,
+                                     const hm_regions* regions, uint64_t* keys_out, uint64_t* counts_out,
+                                     uint32_t* groups_out, int64_t capacity, int64_t* n_out)
+{
+    const HourWindow w = stream_hours(s, hour_lo, hour_hi);
+    if (!s || !regions || !n_out || capacity < 0 || (capacity > 0 && (!keys_out || !counts_out)) ||
+        w.kind == HW_INVALID || group < HM_VIEW_EACH || group > (int64_t)HMS_NOGROUP)
+        return HM_E_ARG;
+    HmsRegionArgs a;
+    int st;
+    if ((st = stream_region_table(s, regions, a))) return st;
+    *n_out = 0;
+    if (a.nspans == 0 || w.kind == HW_EMPTY) return HM_OK;
+    HIPCHK(hipSetDevice(s->ctx->device));
+    /* the view's three passes with the region filter in place of k_stream_view */
+    bool empty;
+    if ((st = stream_filter_begin(s, a.v, &empty)) || empty) return st;
+    stream_region_select(a, w, group);
+    hm_launch_stream_region(s->ctx->stream, a, HMS_RG_SINK_CELLS);
+    HIPCHK(hipGetLastError());
+    return stream_merge_emit(s, keys_out, counts_out, groups_out, nullptr, capacity, n_out);
+}
+
+extern "C" int hm_stream_region_visitors(hm_stream* s, int64_t hour_lo, int64_t hour_hi, const hm_regions* regions,
+                                         int64_t min_visitors, uint64_t* points_out, uint32_t* visitors_out,
+                                         int64_t* withheld_out)
+{
+    const HourWindow w = stream_hours(s, hour_lo, hour_hi);
+    if (!s || !regions || !points_out || !visitors_out || min_visitors < 1 || w.kind == HW_INVALID) return HM_E_ARG;
+    HmsRegionArgs a;
+    int st;
+    if ((st = stream_region_table(s, regions, a))) return st;
+    hm_ctx* ctx = s->ctx;
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t q = ctx->stream;
+    HIPCHK(hipMemsetAsync(points_out, 0, (size_t)a.nregions * 8, q));
+    HIPCHK(hipMemsetAsync(visitors_out, 0, (size_t)a.nregions * 4, q));
+    if (withheld_out) withheld_out[0] = withheld_out[1] = 0;
+    if (a.nspans == 0 || w.kind == HW_EMPTY || s->llen == 0) return HM_OK;
+    /* The filter's records: what finds no slot in a block's table goes out as
+     * it is, at most one record per (survivor, covering span) pair, and every
+     * block writes its table, at most HMS_RG_REC_SLOTS records.  The pass
+     * counts the pairs, so a scratch that turns out short is sized exactly for
+     * the second run. */
+    const uint64_t tables = (uint64_t)hm_stream_region_blocks(s->llen) * HMS_RG_REC_SLOTS;
+    uint64_t cap = s->llen + tables, m = 0;
+    for (int run = 0;; run++) {
+        if ((st = stream_buf(s->rk, cap * 8)) || (st = stream_buf(s->rc, cap * 8))) return st;
+        bool empty;
+        if ((st = stream_filter_begin(s, a.v, &empty))) return st;
+        HIPCHK(hipMemsetAsync(s->state + HMS_ST_PAIRS, 0, 8, q));
+        stream_region_select(a, w, HM_VIEW_EACH);
+        a.capacity = cap;
+        hm_launch_stream_region(q, a, HMS_RG_SINK_RECORDS);
+        HIPCHK(hipGetLastError());
+        if ((st = stream_sync_state(s))) return st;
+        m = s->hstate[HMS_ST_CURSOR];
+        if (m <= cap) break;
+        if (run) return HM_E_HIP;   /* cannot happen: pairs + tables bounds the records */
+        cap = s->hstate[HMS_ST_PAIRS] + tables;
+    }
+    if (m == 0) return HM_OK;
+    /* the distinct (region, group) pairs, then per region their number and their counts' sum */
+    if ((st = stream_buf(s->mk, m * 8)) || (st = stream_buf(s->mc, m * 8))) return st;
+    int64_t nd = 0;
+    if ((st = cells_merge(ctx, (const uint64_t*)s->rk.p, (const uint64_t*)s->rc.p, HM_CELLS_U64, (int64_t)m, nullptr, 0,
+                          (uint64_t*)s->mk.p, (uint64_t*)s->mc.p, (int64_t)m, &nd)))
+        return st;
+    HIPCHK(hipMemsetAsync(s->state + HMS_ST_WCELLS, 0, 2 * 8, q));   /* WCELLS, WPOINTS */
+    hm_launch_region_visit_fold(q, (const uint64_t*)s->mk.p, (const uint64_t*)s->mc.p, (uint64_t)nd, a.nregions,
+                                points_out, visitors_out);
+    hm_launch_region_visit_sweep(q, a.nregions, (uint64_t)min_visitors, points_out, visitors_out, s->state);
+    HIPCHK(hipGetLastError());
+    if ((st = stream_sync_state(s))) return st;
+    if (withheld_out) {
+        withheld_out[0] = (int64_t)s->hstate[HMS_ST_WCELLS];
+        withheld_out[1] = (int64_t)s->hstate[HMS_ST_WPOINTS];
+    }
+    return HM_OK;
+}
+
 /* a raster's tiles, group and log into the kernel's struct: everything but
  * its hours and its grid */
 static void stream_raster_fill(const hm_stream* s, int64_t group, const int64_t* tiles, int ntiles, int bins_log2,
@@ -1481,8 +1683,10 @@ extern "C" int hm_stream_destroy(hm_stream* s)
     if (s->ctx && s->ctx->stream) (void)hipStreamSynchronize(s->ctx->stream);
     for (void* p : {(void*)s->state, (void*)s->bk.keys, (void*)s->bk_alt, (void*)s->bflag, (void*)s->blist,
                     (void*)s->bloc, s->bids.p, s->rec.p, s->plat.p, s->plon.p, s->pkeep.p, s->pstart.p, s->rk.p,
-                    s->rc.p, s->mk.p, s->mc.p, s->tk.p, s->tc.p, s->vt.p, s->vv.p})
+                    s->rc.p, s->mk.p, s->mc.p, s->tk.p, s->tc.p, s->vt.p, s->vv.p, s->gt.p})
         if (p) (void)hipFree(p);
+    if (s->ghost) (void)hipHostFree(s->ghost);
+    if (s->gev) (void)hipEventDestroy(s->gev);
     log_free(s, s->log);
     log_free(s, s->alt);
     if (s->hstate) (void)hipHostFree(s->hstate);

@@ -43,6 +43,13 @@ label is a device rollup of the hour buckets:
                                tile_visitors(tiles, ...) the visitors as grids,
                                and tile_raster / tile_images(..., min_users=k)
                                k-anonymous tiles
+  region_totals / region_series(regions, hours, ...)  the points inside each
+                               region of a region.RegionSet -- polygons, masks:
+                               places that are no rectangle -- in all, or per
+                               frame of the hours (hm_stream_region_series: one
+                               pass, reduced on the device); region_view(...)
+                               the cells inside them, region_visitors(...) the
+                               distinct visitors per region with a threshold
   expire(before_hour)         retention: the cells of hours < before_hour
                                leave the stream, their buckets are freed
   forget(users, groups, hours)  erasure: the cells of these users or group
@@ -84,6 +91,7 @@ import numpy as np
 from . import _lib, device
 from . import heatmap as _hm
 from . import raster as _raster
+from . import region as _region
 from . import top as _top
 
 ALLTIME = -1
@@ -269,6 +277,50 @@ def _frame_args(lo: int, hi: int, frame_hours, trailing):
     if nf > _lib.HM_RASTER_MAX_FRAMES:
         raise ValueError("%d frames; one call takes at most %d" % (nf, _lib.HM_RASTER_MAX_FRAMES))
     return fh, lead, window
+
+
+def _check_regions(regions, zmin: int, zmax: int):
+    """`regions` as a region.RegionSet a stream of zooms zmin..zmax can query.  Pure."""
+    if not isinstance(regions, _region.RegionSet):
+        raise ValueError("regions must be a heatmap_amd.region.RegionSet (got %r)" % (type(regions).__name__,))
+    if not zmin <= regions.zoom <= zmax:
+        raise ValueError("region zoom %d is outside the stream's %d..%d" % (regions.zoom, zmin, zmax))
+    return regions
+
+
+def _region_struct(regions):
+    """(hm_regions of a RegionSet, the arrays it points into: keep them alive for the call)"""
+    arrays = (regions.row_ptr, regions.col_lo, regions.col_hi, regions.region)
+    u32p = ctypes.POINTER(ctypes.c_uint32)
+    rs = _lib.hm_regions(regions.zoom, regions.row_lo, regions.nrows, regions.nspans, regions.nregions,
+                         *(a.ctypes.data_as(u32p) for a in arrays))
+    return rs, arrays
+
+
+def _region_series_args(regions, hours, frame_hours, user, index: dict):
+    """Validated (hour_lo, hour_hi, frame_hours, frames, group word or None) of
+    StreamingHeatmap.region_series on a stream whose group labels are `index`;
+    the group word is tile_raster's (None: a label never seen).  Pure."""
+    lo, hi = int(hours[0]), int(hours[1])
+    if hi <= lo:
+        raise ValueError("a window needs hour_lo < hour_hi (got %d, %d)" % (lo, hi))
+    fh = int(frame_hours)
+    if fh < 1:
+        raise ValueError("frame_hours must be at least 1 (got %r)" % (frame_hours,))
+    nf = -((lo - hi) // fh)
+    if nf * regions.nregions > _lib.HM_REGION_MAX_TOTALS:
+        raise ValueError("%d frames x %d regions; one call takes at most %d totals"
+                         % (nf, regions.nregions, _lib.HM_REGION_MAX_TOTALS))
+    if user is None:
+        gw = _lib.HM_VIEW_MERGED
+    elif user == "all":
+        raise ValueError("a region total counts points: user='all' (the reference's level-weighted 'all' bins) is a "
+                         "property of the row format; use user=None for every kept point")
+    elif not isinstance(user, str):
+        raise ValueError("user must be None or a group label (got %r)" % (user,))
+    else:
+        gw = index.get(user)
+    return lo, hi, fh, nf, gw
 
 
 def _cells_subset(cells: "_hm.Cells", m: np.ndarray) -> "_hm.Cells":
@@ -917,6 +969,114 @@ class StreamingHeatmap:
         (visitors_device, then hm_cells_raster of the keys and visitors)."""
         return self._tile_threshold_raster(tiles, hours, bins_log2, halo, _check_min_visitors(min_users, "min_users"),
                                            "visitors")
+
+    # -------------------------------------------------------------- regions
+
+    def _region_table(self, regions):
+        """(hm_regions struct of a region.RegionSet, the arrays it points into)"""
+        return _region_struct(_check_regions(regions, self.zmin, self.zmax))
+
+    def region_series(self, regions, hours, frame_hours=1, user=None):
+        """int64 CUDA tensor [F, R]: the kept points inside each region of
+        `regions` (a region.RegionSet) per frame of hours = (lo, hi), cut into
+        F = ceil((hi - lo) / frame_hours) frames anchored at lo as tile_frames
+        cuts them -- one chart line per district, or a choropleth per hour --
+        for every group merged (user = None) or the group label `user` (an
+        unknown label: zeros).  A cell inside several regions counts in each.
+        hm_stream_region_series: ONE filter pass over the log with the sums
+        reduced on the device; undated points are in no frame, and the
+        out-of-square side records never belong to a region (spans end at the
+        square)."""
+        torch = self._torch
+        self.ctx.bind_stream()
+        if hours is None:
+            raise ValueError("a series needs hours = (lo, hi): alltime has no first frame (region_totals sums it)")
+        lo, hi, fh, nf, gw = _region_series_args(regions, hours, frame_hours, user, self._index)
+        rs, keep = self._region_table(regions)
+        dev = "cuda:%d" % self.device_index
+        if gw is None:
+            return torch.zeros((nf, regions.nregions), dtype=torch.int64, device=dev)
+        out = torch.empty((nf, regions.nregions), dtype=torch.int64, device=dev)
+        rc = self.ctx.L.hm_stream_region_series(self.ptr, lo, hi, fh, gw, ctypes.byref(rs), device._ptr(out))
+        _lib.raise_for(rc)
+        return out
+
+    def region_totals(self, regions, hours=None, user=None):
+        """int64 CUDA tensor [R]: the kept points inside each region, of hours
+        = None (every kept point, undated ones included) or (lo, hi) -- the
+        sum of region_series over the same hours, as one frame."""
+        torch = self._torch
+        self.ctx.bind_stream()
+        if hours is not None:
+            lo, hi = int(hours[0]), int(hours[1])
+            return self.region_series(regions, hours, max(hi - lo, 1), user)[0]
+        _, _, _, _, gw = _region_series_args(regions, (0, 1), 1, user, self._index)
+        rs, keep = self._region_table(regions)
+        dev = "cuda:%d" % self.device_index
+        if gw is None:
+            return torch.zeros(regions.nregions, dtype=torch.int64, device=dev)
+        out = torch.empty(regions.nregions, dtype=torch.int64, device=dev)
+        rc = self.ctx.L.hm_stream_region_series(self.ptr, _lib.HM_STREAM_ALLTIME, _lib.HM_STREAM_ALLTIME, 1, gw,
+                                                ctypes.byref(rs), device._ptr(out))
+        _lib.raise_for(rc)
+        return out
+
+    def region_view_device(self, regions, hours=None, group="merged"):
+        """(n, keys, counts, groups) as torch CUDA tensors, what view_device
+        returns: the distinct cells that any region of `regions` covers (a cell
+        inside several is listed once), of hours = None or (lo, hi), summed
+        over every group ('merged'), per group ('each') or of one group id
+        (hm_stream_region_view; out-of-square cells never belong to a
+        region)."""
+        self.ctx.bind_stream()
+        rs, keep = self._region_table(regions)
+        _, lo, hi, gw = self._view_args([(self.zmin, 0, 1, 0, 1)], hours, group)
+        # sized as view_device does it: at most the regions' cells for a merged
+        # or one-group view, else from the last such query
+        area = int(regions.area().sum())
+        mk = ("region_view", id(regions), gw if gw < 0 else 0)
+        if gw == _lib.HM_VIEW_EACH:
+            cap = max(1024, int(self._query_n.get(mk, min(area, 1 << 20)) * 1.25) + 1024)
+        else:
+            cap = max(1024, min(area, int(self._query_n.get(mk, 1 << 20) * 1.25) + 1024))
+        cap = min(max(1024, self._log_capacity()), cap)
+        return self._query(lambda *out: self.ctx.L.hm_stream_region_view(self.ptr, lo, hi, gw, ctypes.byref(rs), *out),
+                           1, cap, mk)
+
+    def region_view(self, regions, hours=None, group="merged"):
+        """Host arrays (group u32, zoom, row, col, count) of region_view_device.
+        top.top_cells over region_view_device's keys and counts gives the
+        hottest cells inside a polygon."""
+        n, keys, counts, groups = self.region_view_device(regions, hours, group)
+        return self._host_cells(n, keys, counts, (groups,))
+
+    def region_counts(self, regions, hours=None) -> device.Counts:
+        """Cells of every kept point inside the regions (and the hours)."""
+        _, z, r, c, cnt = self.region_view(regions, hours, "merged")
+        return device.Counts(z, r, c, cnt, 0, [])
+
+    def region_visitors(self, regions, hours=None, min_visitors=1):
+        """(points [R], visitors [R], withheld_regions, withheld_points): per
+        region its kept points and the distinct groups that produced them, as
+        numpy int64 arrays; a region with fewer than min_visitors gets 0 and
+        0, and the last two numbers count those regions (the ones with at
+        least one visitor) and their points.  The records without a group are
+        one visitor together, so visitors is a lower bound on the distinct
+        people (hm_stream_region_visitors; out-of-square cells never belong to
+        a region)."""
+        torch = self._torch
+        self.ctx.bind_stream()
+        m = _check_min_visitors(min_visitors)
+        rs, keep = self._region_table(regions)
+        _, lo, hi, _ = self._view_args([(self.zmin, 0, 1, 0, 1)], hours, "merged")
+        dev = "cuda:%d" % self.device_index
+        pts = torch.empty(regions.nregions, dtype=torch.int64, device=dev)
+        vis = torch.empty(regions.nregions, dtype=torch.int32, device=dev)
+        wh = (ctypes.c_int64 * 2)(0, 0)
+        rc = self.ctx.L.hm_stream_region_visitors(self.ptr, lo, hi, ctypes.byref(rs), m, device._ptr(pts),
+                                                  device._ptr(vis), wh)
+        _lib.raise_for(rc)
+        return (pts.cpu().numpy(), vis.cpu().numpy().view(np.uint32).astype(np.int64), int(wh[0]), int(wh[1]))
 
     # ------------------------------------------------------------- rankings
 

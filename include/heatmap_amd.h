@@ -616,6 +616,68 @@ int hm_stream_visitors(hm_stream* s, int64_t hour_lo, int64_t hour_hi, const int
                        int64_t min_visitors, uint64_t* keys_out, uint64_t* points_out, uint32_t* visitors_out,
                        int64_t capacity, int64_t* n_out, int64_t* withheld_out);
 
+/* Regions: places whose outline is not a rectangle -- a district, a geofence,
+ * the polygons of a choropleth.  A region set is up to HM_REGION_MAX_REGIONS
+ * regions, each a set of cells of ONE zoom (one of the stream's), given as row
+ * spans in CSR form: the rows [row_lo, row_lo + nrows); row i's spans at
+ * [row_ptr[i], row_ptr[i + 1]) (row_ptr: nrows + 1 words, from 0 to nspans);
+ * span j the columns [col_lo[j], col_hi[j]) of region[j].  Within a row the
+ * spans are sorted by (col_lo, region), col_lo < col_hi <= 2^zoom, region <
+ * nregions, and the spans of one region do not overlap; spans of different
+ * regions may, and a cell then belongs to each of them.  A row may have no
+ * span, and so may the table (nspans = 0: nothing is selected).  The arrays are
+ * host memory; every call validates them, then uploads them.  A table that
+ * breaks a rule is HM_E_ARG with nothing written, and hm_last_error's index is
+ * the first offending span (or row, for row_ptr).  The out-of-square side
+ * records a caller keeps beside the stream never belong to a region: spans
+ * end at the square.  The hours are hm_stream_view's: [hour_lo, hour_hi)
+ * clamped (undated cells are in no range), or the HM_STREAM_ALLTIME pair:
+ * everything, undated cells included; a window wholly outside the stream's
+ * hours selects nothing and is HM_OK.  The log is left exactly as it is.
+ *
+ *   hm_stream_region_series    totals_out (device u64 [F][nregions]): the sum
+ *                     of the counts of region r's cells per frame of the hours,
+ *                     F = ceil((hour_hi - hour_lo) / frame_hours) frames
+ *                     anchored at hour_lo as hm_stream_raster_frames cuts them;
+ *                     the HM_STREAM_ALLTIME pair is ONE frame and frame_hours
+ *                     is not read.  group = HM_VIEW_MERGED or one group id.  A
+ *                     cell inside several regions adds to each.  Every entry is
+ *                     written, zeros included.  HM_E_ARG: a null pointer, a
+ *                     refused table, HM_VIEW_EACH, hour_hi <= hour_lo,
+ *                     frame_hours < 1, F * nregions > HM_REGION_MAX_TOTALS.
+ *                     One filter pass with the sums reduced on the device;
+ *                     asynchronous, nothing is read back.
+ *   hm_stream_region_view      the distinct cells that any region covers, each
+ *                     once, with their summed counts: outputs, capacity, *n_out,
+ *                     HM_E_CAPACITY and group (HM_VIEW_MERGED, HM_VIEW_EACH, a
+ *                     group id) exactly as hm_stream_view's.
+ *   hm_stream_region_visitors  per region its points (points_out, device u64
+ *                     [nregions]) and the distinct group ids that own a selected
+ *                     record inside it (visitors_out, device u32 [nregions]);
+ *                     the records without a group are one visitor together, as
+ *                     in hm_stream_visitors.  A region with fewer than
+ *                     min_visitors (>= 1) gets 0 and 0; withheld_out (host
+ *                     int64[2], may be NULL) counts the regions with 1 <=
+ *                     visitors < min_visitors and their points.  Every entry
+ *                     is written.  Waits for the numbers it returns. */
+#define HM_REGION_MAX_REGIONS 4096
+#define HM_REGION_MAX_SPANS (1 << 20)
+#define HM_REGION_MAX_ROWS (1 << 20)
+#define HM_REGION_MAX_TOTALS (1 << 22)   /* frames * regions of one series call */
+typedef struct hm_regions {              /* host arrays; validated, then uploaded */
+    int zoom;
+    int64_t row_lo, nrows, nspans, nregions;
+    const uint32_t *row_ptr, *col_lo, *col_hi, *region;
+} hm_regions;
+int hm_stream_region_series(hm_stream* s, int64_t hour_lo, int64_t hour_hi, int64_t frame_hours, int64_t group,
+                            const hm_regions* regions, uint64_t* totals_out);
+int hm_stream_region_view(hm_stream* s, int64_t hour_lo, int64_t hour_hi, int64_t group, const hm_regions* regions,
+                          uint64_t* keys_out, uint64_t* counts_out, uint32_t* groups_out, int64_t capacity,
+                          int64_t* n_out);
+int hm_stream_region_visitors(hm_stream* s, int64_t hour_lo, int64_t hour_hi, const hm_regions* regions,
+                              int64_t min_visitors, uint64_t* points_out, uint32_t* visitors_out,
+                              int64_t* withheld_out);
+
 /* Multi-GPU exchange of hm_count cells (one process per GPU; the collectives
  * are RCCL calls made by the caller, heatmap_amd/multigpu.py).  They replace
  * the reference's two shuffles, reduceByKey (heatmap.py:111) and groupByKey

@@ -139,6 +139,26 @@ results compared record by record.  --each-only times the earlier route alone
 (nothing newer than hm_stream_view and hm_stream_import is needed, so a
 checkout of the parent commit can run it); --parent-json FILE puts that run's
 times into this one's result as "parent_each_unique_ms".
+
+    python tools/bench_stream.py --retain 24 --batches 30 --warmup 0 --regions --out profiles/stream_regions.json
+
+--retain H --regions: polygon regions (heatmap_amd.region, hm_stream_region_*)
+on the steady retained log, trailing 24 hours: (a) one polygon, the ellipse
+inscribed in --top's 4 x 3-tile screen at the detail zoom: its total
+(region_totals) and its cells (region_view_device); (b) a choropleth of about
+1000 polygons, a jittered 32 x 32 mesh of quadrilaterals over the 256 x 256
+zoom-14 cells around the heaviest one: totals and a 24-frame hourly series
+(region_series); (c) region_visitors(min_visitors=5) on (b), on --top's
+grouped copy of the log.  Each against the route a caller had before:
+view_device of the bounding rectangle, every returned cell looked up in a
+dense region-id image in torch, scatter_add (24 such calls for the series;
+view_device(..., 'each'), torch.unique of (region, group) and scatter_add for
+the visitors).  Both routes are warmed, then take REGION_REPS alternating
+repetitions, timed and reported as above, and the two results are compared
+entry for entry (the cells record for record).  --bbox-only times the earlier
+routes alone (nothing newer than hm_stream_view is called; region.py is host
+code); --parent-json FILE puts that run's times into this one's result as
+"parent_bbox_ms".
 """
 import argparse
 import json
@@ -890,6 +910,175 @@ def visitors_bench(s, a, lo, hi):
     return out
 
 
+REGION_REPS = 25
+
+
+def _region_image(rs):
+    """(bounding rectangle, int32 CUDA image of it: region + 1 per cell, 0 outside) of a RegionSet whose
+    regions do not overlap: what the bounding-box route looks cells up in"""
+    import numpy as np
+
+    box = rs.bounding_rect()
+    w = box[4] - box[3]
+    d = np.zeros((rs.nrows, w + 1), dtype=np.int64)
+    rows = rs.rows() - rs.row_lo
+    np.add.at(d, (rows, rs.col_lo.astype(np.int64) - box[3]), rs.region.astype(np.int64) + 1)
+    np.add.at(d, (rows, rs.col_hi.astype(np.int64) - box[3]), -(rs.region.astype(np.int64) + 1))
+    return box, torch.from_numpy(np.cumsum(d, axis=1)[:, :w].astype(np.int32)).cuda()
+
+
+def _choropleth(s, a, h24, zb):
+    """about 1000 polygons tiling the 256 x 256 zoom-zb cells around the heaviest zoom-zb cell of the hours:
+    a 32 x 32 mesh of quadrilaterals with jittered inner corners, rasterised (RegionSet.from_tile_polygons)
+    and made disjoint through the region image, so the bounding-box route can hold it"""
+    import numpy as np
+
+    from heatmap_amd.region import RegionSet
+
+    n, keys, counts, _ = s.window_device(*h24)
+    kb, cb = keys[:n][(keys[:n] >> 58) == zb], counts[:n][(keys[:n] >> 58) == zb]
+    heavy = int(kb[torch.argmax(cb)].item())
+    side = 1 << zb
+    r0 = min(max(((heavy >> 29) & 0x1FFFFFFF) - 128, 0), max(side - 256, 0))
+    c0 = min(max((heavy & 0x1FFFFFFF) - 128, 0), max(side - 256, 0))
+    rng = np.random.default_rng(14)
+    gy, gx = np.meshgrid(np.arange(33) * 8.0, np.arange(33) * 8.0, indexing="ij")
+    jit = rng.uniform(-2.5, 2.5, (2, 33, 33))
+    jit[:, [0, -1], :] = 0
+    jit[:, :, [0, -1]] = 0
+    px, py = c0 + gx + jit[0], r0 + gy + jit[1]
+    polys = [[np.array([[px[i, j], py[i, j]], [px[i, j + 1], py[i, j + 1]], [px[i + 1, j + 1], py[i + 1, j + 1]],
+                        [px[i + 1, j], py[i + 1, j]]])] for i in range(32) for j in range(32)]
+    rs = RegionSet.from_tile_polygons(polys, zb)
+    img = np.zeros((min(256, side), min(256, side)), dtype=np.int64)
+    for j in range(rs.nregions):                  # a cell two quadrilaterals claim (rounding on a shared edge) stays one's
+        r, c = rs.cells(j)
+        img[r - r0, c - c0] = j + 1
+    return RegionSet.from_mask(zb, r0, c0, img)
+
+
+def _region_checksum(b):
+    """one number of a route's result, to tell that two runs answered the same question"""
+    if torch.is_tensor(b):
+        return int(b.sum().item())
+    if torch.is_tensor(b[1]):
+        return int(b[1].sum().item())
+    return int(b[0].sum() + b[1].sum())
+
+
+def regions_bench(s, a, lo, hi):
+    """--regions / --bbox-only (module docstring) on the stream as it stands"""
+    import numpy as np
+
+    from heatmap_amd.region import RegionSet
+
+    h24 = (max(lo, hi - 24), hi)
+    screen = _hot_screen(s, a, h24)
+    r0, r1 = min(q[1] for q in screen), max(q[2] for q in screen)
+    c0, c1 = min(q[3] for q in screen), max(q[4] for q in screen)
+    t = np.linspace(0.0, 2.0 * np.pi, 256, endpoint=False)
+    ring = np.stack([(c0 + c1) / 2 + (c1 - c0) / 2 * np.cos(t), (r0 + r1) / 2 + (r1 - r0) / 2 * np.sin(t)], axis=1)
+    ell = RegionSet.from_tile_polygons([[ring]], a.zmax)
+    zb = min(14, a.zmax)
+    cho = _choropleth(s, a, h24, zb)
+    g = _grouped_copy(s, a)
+    out = {"hours": list(h24), "reps": REGION_REPS, "log_cells": s.cells()[0],
+           "timing": "host ms around the route plus one synchronise; both routes warmed, then alternating",
+           "bbox_route": "view_device of the bounding rectangle, a lookup of every returned cell in a dense "
+                         "region-id image in torch, scatter_add (24 such calls for the series; "
+                         "view_device(..., 'each'), torch.unique of (region, group) and scatter_add for visitors)",
+           "groups": "visitors: 1000 groups, group = a hash of the cell (the --visitors copy of the log)"}
+
+    def lookup(img, box, k):
+        return img[((k >> 29) & 0x1FFFFFFF) - box[1], (k & 0x1FFFFFFF) - box[3]].to(torch.int64)
+
+    def bbox_totals(rs, img, box, hours=h24):
+        nv, vk, vc, _ = s.view_device([box], hours)
+        tot = torch.zeros(rs.nregions + 1, dtype=torch.int64, device="cuda")
+        return tot.scatter_add_(0, lookup(img, box, vk[:nv]), vc[:nv])[1:]
+
+    def bbox_cells(rs, img, box):
+        nv, vk, vc, _ = s.view_device([box], h24)
+        m = lookup(img, box, vk[:nv]) > 0
+        return vk[:nv][m], vc[:nv][m]
+
+    def bbox_series(rs, img, box):
+        return torch.stack([bbox_totals(rs, img, box, (h, h + 1)) for h in range(*h24)])
+
+    def bbox_visitors(rs, img, box):
+        nv, vk, vc, vg = g.view_device([box], h24, "each")
+        reg = lookup(img, box, vk[:nv])
+        m = reg > 0
+        pairs = torch.unique(((reg[m] - 1) << 32) | (vg[:nv][m].to(torch.int64) & 0xFFFFFFFF))
+        vis = torch.bincount(pairs >> 32, minlength=rs.nregions)
+        pts = torch.zeros(rs.nregions + 1, dtype=torch.int64, device="cuda").scatter_add_(0, reg, vc[:nv])[1:]
+        low = (vis >= 1) & (vis < 5)
+        wr, wp = int(low.sum().item()), int(pts[low].sum().item())
+        return torch.where(vis < 5, 0, pts).cpu().numpy(), torch.where(vis < 5, 0, vis).cpu().numpy(), wr, wp
+
+    def region_cells(rs, img, box):
+        n, k, c, _ = s.region_view_device(rs, h24)
+        return k[:n], c[:n]
+
+    def same_cells(x, y):
+        ox, oy = torch.argsort(x[0]), torch.argsort(y[0])
+        return torch.equal(x[0][ox], y[0][oy]) and torch.equal(x[1][ox], y[1][oy])
+
+    def same_visitors(x, y):
+        return np.array_equal(x[0], y[0]) and np.array_equal(x[1], y[1]) and x[2:] == y[2:]
+
+    cases = [("a_ellipse_z%d_totals" % a.zmax, ell, bbox_totals, lambda rs, i, b: s.region_totals(rs, h24), torch.equal),
+             ("a_ellipse_z%d_cells" % a.zmax, ell, bbox_cells, region_cells, same_cells),
+             ("b_choropleth_z%d_totals" % zb, cho, bbox_totals, lambda rs, i, b: s.region_totals(rs, h24), torch.equal),
+             ("b_choropleth_z%d_series24" % zb, cho, bbox_series, lambda rs, i, b: s.region_series(rs, h24, 1),
+              torch.equal),
+             ("c_choropleth_z%d_visitors_min5" % zb, cho, bbox_visitors,
+              lambda rs, i, b: g.region_visitors(rs, h24, 5), same_visitors)]
+    images = {id(rs): _region_image(rs) for rs in (ell, cho)}
+    ok = True
+    for name, rs, old, new, same in cases:
+        box, img = images[id(rs)]
+        routes = [("bbox_ms", old)] + ([] if a.bbox_only else [("region_ms", new)])
+        t = {key: [] for key, _ in routes}
+        last = {}
+        for key, f in routes:
+            f(rs, img, box)                   # warm: code objects, the capacity memo, the scratch
+            f(rs, img, box)
+        for _ in range(REGION_REPS):
+            for key, f in routes:
+                ms, last[key] = _ms(lambda: f(rs, img, box))
+                t[key].append(ms)
+        res = {"regions": rs.nregions, "spans": rs.nspans, "rows": rs.nrows, "region_cells": int(rs.area().sum()),
+               "bounding_rect": [int(v) for v in box]}
+        res["checksum"] = _region_checksum(last["bbox_ms"])
+        for key in t:
+            res[key] = _stats(t[key])
+        if not a.bbox_only:
+            eq = bool(same(last["bbox_ms"], last["region_ms"]))
+            ok &= eq
+            res["region_equals_bbox_route"] = eq
+            o, w = res["bbox_ms"], res["region_ms"]
+            res["verdict"] = ("not distinguishable" if w["min"] <= o["max"] and o["min"] <= w["max"] else
+                              "region faster" if w["median"] < o["median"] else "region slower")
+        out[name] = res
+    g.close()
+    if not a.bbox_only:
+        out["check"] = "ok" if ok else "FAIL"
+    if a.parent_json:
+        pj = json.load(open(a.parent_json))["regions"]
+        assert pj["log_cells"] == out["log_cells"] and pj["hours"] == out["hours"]
+        for name, *_ in cases:
+            assert pj[name]["checksum"] == out[name]["checksum"]
+            out[name]["parent_bbox_ms"] = pj[name]["bbox_ms"]
+            o, w = pj[name]["bbox_ms"], out[name]["region_ms"]
+            out[name]["verdict_vs_parent"] = ("not distinguishable" if w["min"] <= o["max"] and o["min"] <= w["max"]
+                                              else "region faster" if w["median"] < o["median"] else "region slower")
+        out["parent_note"] = ("this script with --regions --bbox-only run by a checkout of the parent commit (its "
+                              "library and package, this commit's heatmap_amd/region.py beside it) on the same seeded "
+                              "log, in the same session")
+    return out
+
+
 def retain(a):
     """--retain H: a stream under retention (module docstring)"""
     n, H = int(a.batch), a.retain
@@ -925,6 +1114,7 @@ def retain(a):
     fgt = forget_bench(s, a, BASE + total - 1 - H, BASE + total) if a.forget or a.expire_only else None
     top = top_bench(s, a, BASE + total - 1 - H, BASE + total) if a.top or a.sort_only else None
     vis = visitors_bench(s, a, BASE + total - 1 - H, BASE + total) if a.visitors or a.each_only else None
+    reg = regions_bench(s, a, BASE + total - 1 - H, BASE + total) if a.regions or a.bbox_only else None
     result = json.dumps({
         "metric": "stream under retention: expire(newest - H) and window(newest - H, newest + 1) per one-hour batch",
         "retain_hours": H, "batch_points": n, "batches": a.batches, "warmup": a.warmup, "zooms": [a.zmin, a.zmax],
@@ -944,6 +1134,7 @@ def retain(a):
         "forget": fgt,
         "top": top,
         "visitors": vis,
+        "regions": reg,
         "series": series,
         "data": "synthetic (heatmap_amd.synth, generated on device, resident in HBM)"})
     print(result)
@@ -991,6 +1182,11 @@ def main():
                     help="with --retain 24 or more: the cells with at least 5 distinct visitors (hm_stream_visitors) "
                          "against a per-group view, a device unique and a mask (module docstring)")
     ap.add_argument("--each-only", action="store_true", help="with --retain: --visitors' view-and-unique route alone")
+    ap.add_argument("--regions", action="store_true",
+                    help="with --retain 24 or more: totals, cells, a 24-hour series and visitors of polygon regions "
+                         "(hm_stream_region_*) against a view of the bounding rectangle and a lookup in a region-id "
+                         "image (module docstring)")
+    ap.add_argument("--bbox-only", action="store_true", help="with --retain: --regions' bounding-box routes alone")
     ap.add_argument("--readd-only", action="store_true",
                     help="with --retain: time only the re-adding of the retained batches to a fresh stream")
     ap.add_argument("--parent-json", default=None, metavar="FILE",
@@ -999,7 +1195,7 @@ def main():
                          "--view-only result, kept as parent_view_ms; with --frames: its --loop-only result, kept as "
                          "parent_loop_ms; with --forget: its --expire-only result, kept as parent_expire_ms; with "
                          "--top: its --sort-only result, kept as parent_sort_ms; with --visitors: its --each-only result, kept as "
-                         "parent_each_unique_ms")
+                         "parent_each_unique_ms; with --regions: its --bbox-only result, kept as parent_bbox_ms")
     ap.add_argument("--out", default=None, metavar="FILE", help="with --retain: also write the JSON line to FILE")
     a = ap.parse_args()
     if a.retain > 0:
